@@ -13,12 +13,17 @@ evaluation per pair, genome window gather included.  Pairs are independent, so
 ranks process their own shards with no collective on the data path (weak
 scaling); the only collectives are the timing barrier and the max-over-ranks.
 
-Also reported: ``roofline`` (the kernel's HBM fraction, its PMC traffic, and the ceiling of its
-access pattern), ``cpu_baseline`` (the reference's path restated literally in Python, over a
+A plain run sets up, warms up, times the steps and prints the line; its ``roofline`` holds the
+kernel's HBM fraction from the timed launches and the recorded PMC traffic.  ``--dump-outputs DIR``
+also writes the last timed step's results (a seeded sample of the batch; the inputs are seeded too,
+so two builds can be compared file for file) as DIR/<name>.npy.  Every other leg runs with
+``--full`` only: ``roofline.access_pattern_ceiling`` (the ceiling of the kernel's access pattern),
+the check of the compact words against the 8-byte scan, ``cpu_baseline`` (the reference's path
+restated literally in Python, over a
 process pool of the GPU's CPU share; 1-process and C legs in ``cpu_baseline_extra``),
 ``strong_scaling`` (configs[3]) and ``configs4_200M_150bp``; ``extra``: configs[1] (1M pairs on
 CDR1as_locus.fa), the configs[4] per-GPU share, and the whole CLI in anchor pairs/s at 2M and 20M
-reads (BAM on stdin).  ``--research`` adds the forms DESIGN.md §5 compares (pipelines, window-carrying,
+reads (BAM on stdin).  ``--full --research`` adds the forms DESIGN.md §5 compares (pipelines, window-carrying,
 wave-per-pair, reorder-then-scan, locus-ordered).
 """
 from __future__ import annotations
@@ -72,6 +77,12 @@ def parse():
     ap.add_argument("--read-len", type=int, default=100)
     ap.add_argument("--locus-ordered", dest="locus_ordered", action="store_true",
                     help="lay the batch out by A-window locus (PairBatch.pack(locus_order=True)); default read order")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg: configs[3] strong scaling, configs[4], the "
+                         "access-pattern ceiling, the CPU baselines, the extras, the compact-word check "
+                         "(the --no-* options below switch single legs of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (a seeded sample of the batch) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the extras (configs[1], the configs[4] 150-bp share, the CLI end to end)")
@@ -90,7 +101,12 @@ def parse():
     ap.add_argument("--no-cli", action="store_true", help="skip the end-to-end CLI extra (2M reads, BAM on stdin)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget per CPU baseline leg")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_r06.json"))
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps is at least 1")
+    if args.research and not args.full:
+        ap.error("--research adds to the legs of --full: give both")
+    return args
 
 
 def setup_dist(args):
@@ -464,7 +480,7 @@ def configs4(opt, g, ws, rank, dev, steps, warmup, total=200_000_000):
               span_min=150, span_max=20000, p_three_seg=CONFIG5_THREE_SEG)
     b = stream_share(opt, g, kw, lo, hi)
     bmean = mean_algo_bytes(b, opt.asize, opt.margin)
-    elapsed, kms, out = timed_scans(opt, g, b, steps, warmup, ws, dev)
+    elapsed, kms, out, _ = timed_scans(opt, g, b, steps, warmup, ws, dev)
     elapsed = max_over_ranks(elapsed, ws, dev)
     kms = max_over_ranks(kms, ws, dev)
     hits = int(((out.results[:n] & 0xFFFF) != 0xFFFF).sum())
@@ -522,11 +538,12 @@ def reorder_then_scan(opt, g, b, steps, dev, bpp):
                     "events); the headline keeps the read-order scan because this sum is larger"}
 
 
-def timed_scans(opt, g, b, steps, warmup, ws, dev, compact_width=0):
+def timed_scans(opt, g, b, steps, warmup, ws, dev, compact_width=0, check=True):
     """Warmup, then exactly `steps` scans bracketed by barrier + synchronize; per-launch HIP events.
     compact_width 2 / 4: the scans write their results in that compact form themselves
-    (fc2_bp_scan_compact_launch into device memory, canonical mode), and after the timed region the
-    words, expanded on the host, must equal the 8-byte scan's results word for word."""
+    (fc2_bp_scan_compact_launch into device memory, canonical mode), and with `check` the words,
+    expanded on the host after the timed region, must equal the 8-byte scan's results word for word.
+    Returns (seconds, mean kernel ms, the 8-byte ScanOutput, the CompactResults or None)."""
     import torch
     from find_circ2_amd import CompactResults, scan
     from find_circ2_amd.hotpath import expand, scan_compact
@@ -558,7 +575,7 @@ def timed_scans(opt, g, b, steps, warmup, ws, dev, compact_width=0):
     barrier(ws)
     t1 = time.perf_counter()
     kms = [s.elapsed_time(e) for s, e in ev]
-    if c is not None:                     # the compact words are the 8-byte results, exactly
+    if c is not None and check:           # the compact words are the 8-byte results, exactly
         k = int(c.count.item())
         if k > c.cap:
             raise RuntimeError("compact headline: %d escapes, %d slots" % (k, c.cap))
@@ -567,7 +584,46 @@ def timed_scans(opt, g, b, steps, warmup, ws, dev, compact_width=0):
         words = c.words[:b.n].cpu().numpy()
         if not np.array_equal(expand(opt, words, esc), out.results[:b.n].cpu().numpy()):
             raise RuntimeError("compact headline: expanded words differ from the 8-byte scan")
-    return t1 - t0, float(np.mean(kms)), out
+    return t1 - t0, float(np.mean(kms)), out, c
+
+
+def dump_outputs(d, opt, b, out, c, rank, max_sample=1 << 20):
+    """--dump-outputs: what the timed path's last step left for its caller, as float .npy files under
+    `d` (rank r > 0 appends ``_rank<r>`` to the names).  The pairs written are a fixed, seeded sample
+    of the batch (all of it when it is no larger): ``sample_index`` (float64, ascending pair indices),
+    ``results`` (float32 [m, 5]: best_x, dist, ov, n_ties, info of each sampled pair's 8-byte result),
+    and for a compact headline scan ``compact_words`` (float32: the 2- or 4-byte words the scan wrote,
+    as unsigned integers) and ``escape_count`` (float64 [1]: escapes of the whole batch).  The sampled
+    compact words are expanded on the host (fc2_result_expand) with the escapes that fall in the sample."""
+    import torch
+    from find_circ2_amd import _native as N
+    from find_circ2_amd.hotpath import expand
+    n = b.n
+    if n > max_sample:
+        idx = np.sort(np.random.default_rng(20240607).choice(n, max_sample, replace=False)).astype(np.int64)
+    else:
+        idx = np.arange(n, dtype=np.int64)
+    didx = torch.from_numpy(idx).to(b.device)
+    files = {"sample_index": idx.astype(np.float64)}
+    if c is not None:
+        k = int(c.count.item())
+        if k > c.cap:
+            raise RuntimeError("dump-outputs: %d escapes, %d slots" % (k, c.cap))
+        words = c.words[:n][didx].cpu().numpy().view(np.uint16 if c.width == 2 else np.uint32)
+        esc = c.esc[:2 * k].cpu().numpy().view(N.ESCAPE_DTYPE).copy()
+        pos = np.searchsorted(idx, esc["index"].astype(np.int64))
+        inside = (pos < len(idx)) & (idx[np.minimum(pos, len(idx) - 1)] == esc["index"].astype(np.int64))
+        esc = esc[inside]
+        esc["index"] = pos[inside]
+        res = expand(opt, words, esc).view(N.RESULT_DTYPE)
+        files["compact_words"] = words.astype(np.float32 if c.width == 2 else np.float64)
+        files["escape_count"] = np.array([k], np.float64)
+    else:
+        res = out.results[:n][didx].cpu().numpy().view(N.RESULT_DTYPE)
+    files["results"] = np.stack([res[f].astype(np.float32) for f in ("best_x", "dist", "ov", "n_ties", "info")], axis=1)
+    os.makedirs(d, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ("_rank%d" % rank if rank else "") + ".npy"), a)
 
 
 def strong_scaling(opt, g, b0, ref64, ws, rank, dev, steps, warmup, n, cfg_kw, per_rank=4, streams=None, tail=0):
@@ -1257,10 +1313,14 @@ def main():
     # for results that do not fit, none on this workload): 2.2 % faster than 8-byte words in a
     # same-process A/B (profiles/r04/ab_compact_headline.jsonl), checked word for word after timing
     cw = 0 if (opt.noncanonical or opt.allhits) else HEADLINE_RESULT_BYTES
-    elapsed, kernel_ms, out = timed_scans(opt, g, b, args.steps, args.warmup, ws, dev, compact_width=cw)
+    elapsed, kernel_ms, out, comp = timed_scans(opt, g, b, args.steps, args.warmup, ws, dev, compact_width=cw,
+                                                check=args.full)
     elapsed = max_over_ranks(elapsed, ws, dev)
     kernel_ms = max_over_ranks(kernel_ms, ws, dev)
     mark("timed_scans")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, opt, b, out, comp, rank)
+        mark("dump_outputs")
     total_pairs = b.n * args.steps * ws
     value = total_pairs / elapsed
     bpp = algo_bytes_per_pair(args.read_len, opt.asize, opt.margin, result_bytes=cw or 8)
@@ -1282,16 +1342,16 @@ def main():
                                "hbm_bytes_per_pair": w.get("hbm_bytes_per_pair")}
         except Exception:
             traffic = None
-    res = out.host(b.n)
-    hits = int((res["best_x"] >= 0).sum())
-    b._bench_ref_results = torch.from_numpy(res.view(np.int64).copy())
+    hits = int(((out.results[:b.n] & 0x8000) == 0).sum())      # best_x (the low int16 of a result) >= 0
+    if args.full:                                # the 8-byte results every other leg checks itself against
+        b._bench_ref_results = torch.from_numpy(out.host(b.n).view(np.int64).copy())
     c4 = None
-    if args.workload == "hg19" and not args.no_config4 and (args.config4_pairs or not args.pairs):
+    if args.full and args.workload == "hg19" and not args.no_config4 and (args.config4_pairs or not args.pairs):
         c4 = configs4(opt, g, ws, rank, dev, args.steps, args.warmup, total=args.config4_pairs or 200_000_000)
         mark("configs4")
     # configs[3]: rank 0's stream strong-scaled over the ranks with the host-side ordered merge
     strong = None
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         n0, kw0 = workload_cfg(args, 0)
         strong = strong_scaling(opt, g, b if rank == 0 else None, b._bench_ref_results.numpy() if rank == 0 else None,
                                 ws, rank, dev, args.steps, args.warmup, n0, kw0, per_rank=args.strong_batches or max(2, 8 // ws),
@@ -1334,7 +1394,7 @@ def main():
     if traffic:
         # HBM bytes moved per algorithmic byte (the random 19-B windows each cost whole 128-B lines)
         line["roofline"]["traffic_ratio"] = round(traffic / (bpp * b.n), 3)
-    if args.workload == "hg19" and not args.locus_ordered and b.n == 50_000_000:
+    if args.full and args.workload == "hg19" and not args.locus_ordered and b.n == 50_000_000:
         pc = pattern_ceiling(opt, g, b, dev)
         mark("pattern_ceiling")
         line["roofline"]["access_pattern_ceiling"] = pc
@@ -1346,14 +1406,14 @@ def main():
             bpp8 = algo_bytes_per_pair(args.read_len, opt.asize, opt.margin, result_bytes=8)
             line["roofline"]["ceiling_frac"] = round(bpp8 * b.n / (pc["probe_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
             line["roofline"]["scan_frac_of_ceiling"] = pc["scan_frac_of_ceiling"]
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu_baseline:
         cb = cpu_baselines(opt, g, b, args.cpu_seconds)
         mark("cpu_baselines")
         line["cpu_baseline"] = cb["main"]
         line["cpu_baseline_extra"] = {"python_1core": cb["python_1core"], "python_pool": cb["python_pool"],
                                       "c_naive_1core": cb["c_naive"], "c_fast_allcores": cb["c_fast"],
                                       "cpu_model": cb["cpu_model"]}
-    if rank == 0 and ws == 1 and not args.no_extra and args.workload == "hg19":
+    if args.full and rank == 0 and ws == 1 and not args.no_extra and args.workload == "hg19":
         line["extra"] = {}
         if args.research:
             # the forms and pipelines DESIGN.md §5 compares the headline with (opt-in: --research)
@@ -1371,7 +1431,7 @@ def main():
         a2 = argparse.Namespace(**vars(args))
         a2.workload, a2.pairs = "cdr1as", 1_000_000
         o2, g2, b2 = build_workload(a2, rank, dev)
-        el2, km2, _ = timed_scans(o2, g2, b2, max(args.steps, 20), args.warmup, 1, dev)
+        el2, km2, _, _ = timed_scans(o2, g2, b2, max(args.steps, 20), args.warmup, 1, dev)
         line["extra"]["configs[1]_cdr1as_1M"] = {
             "value": round(b2.n * max(args.steps, 20) / el2, 1), "unit": "anchor-pairs/s",
             "kernel_ms": round(km2, 4),
@@ -1384,7 +1444,7 @@ def main():
             a3 = argparse.Namespace(**vars(args))
             a3.locus_ordered = True
             o3, g3, b3 = build_workload(a3, rank, dev)
-            el3, km3, _ = timed_scans(o3, g3, b3, args.steps, args.warmup, 1, dev)
+            el3, km3, _, _ = timed_scans(o3, g3, b3, args.steps, args.warmup, 1, dev)
             ach3 = bpp * b3.n / (km3 * 1e-3) / 1e9
             line["extra"]["configs[2]_locus_ordered_batch"] = {
                 "value": round(b3.n * args.steps / el3, 1), "unit": "anchor-pairs/s", "kernel_ms": round(km3, 4),
@@ -1398,7 +1458,7 @@ def main():
         a4.pairs, a4.read_len, a4.read_len_min = 25_000_000, 150, 120
         o4, g4, b4 = build_workload(a4, rank, dev)
         bm4 = mean_algo_bytes(b4, o4.asize, o4.margin)
-        el4, km4, _ = timed_scans(o4, g4, b4, args.steps, args.warmup, 1, dev)
+        el4, km4, _, _ = timed_scans(o4, g4, b4, args.steps, args.warmup, 1, dev)
         bpp4 = algo_bytes_per_pair(150, o4.asize, o4.margin)
         line["extra"]["configs[4]_150bp_variable_per_gpu_share"] = {
             "value": round(b4.n * args.steps / el4, 1), "unit": "anchor-pairs/s", "kernel_ms": round(km4, 4),

@@ -37,7 +37,8 @@ def test_launcher_fails_when_ranks_fail():
 @pytest.mark.gpu
 def test_two_ranks_strong_scaling_merge_equals_single_rank():
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cdr1as",
-                        "--pairs", "1000000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra"],
+                        "--pairs", "1000000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                        "--no-extra"],
                        env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -48,9 +49,72 @@ def test_two_ranks_strong_scaling_merge_equals_single_rank():
     assert st["value"] > 0 and line["value"] > 0
 
 
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_results(tmp_path):
+    """A plain run (no --full) runs the headline alone -- exactly --steps timed steps, no other leg -- and
+    --dump-outputs writes the results a direct scan of the same seeded workload gives, as float arrays."""
+    import argparse
+    import numpy as np
+    import torch
+    import bench
+    from find_circ2_amd import scan
+    d = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cdr1as",
+                        "--pairs", "200000", "--steps", "2", "--warmup", "1", "--dump-outputs", d],
+                       env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert abs(200000 / line["value"] * 1e3 - line["ms_per_step"]) <= 1e-4     # value: pairs per second of a step
+    assert line["strong_scaling"] is None and line["configs4_200M_150bp"] is None and line["cpu_baseline"] is None
+    assert "extra" not in line and "access_pattern_ceiling" not in line["roofline"]
+    assert set(line["legs_s"]) == {"workload", "timed_scans", "dump_outputs"}
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert set(got) == {"sample_index", "results", "compact_words", "escape_count"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["sample_index"], np.arange(200000))
+    dev = torch.device("cuda", 0)
+    args = argparse.Namespace(workload="cdr1as", pairs=200000, read_len=100, locus_ordered=False)
+    opt, g, b = bench.build_workload(args, 0, dev)
+    ref = scan(opt, g, b).host(b.n)
+    for k, f in enumerate(("best_x", "dist", "ov", "n_ties", "info")):
+        assert np.array_equal(got["results"][:, k], ref[f].astype(np.float32)), f
+    assert line["config"]["pairs_with_hit"] == int((ref["best_x"] >= 0).sum())
+
+
+@pytest.mark.gpu
+def test_dump_outputs_samples_a_batch_with_escapes(tmp_path):
+    """bench.dump_outputs on a batch larger than its sample, with many escaped compact words (long
+    reads, -d 6): the sampled rows are the 8-byte scan's results at sample_index, field for field."""
+    import numpy as np
+    import torch
+    import bench
+    from find_circ2_amd import CompactResults, Options, compact
+    from find_circ2_amd import _native as N
+    from synth_small import load_genome, make_spans
+    from test_gpu_parity import genome, run_spans
+    path = os.path.join(ROOT, "tests", "golden", "CDR1as_locus.fa")
+    opt = Options(maxdist=6, margin=0)
+    spans = make_spans(load_genome(path), 6000, seed=606, asize=opt.asize, L=(60, 300), p_readN=0.05)
+    b, out = run_spans(opt, genome(path), spans)
+    c = compact(opt, out.results, b.n, into=CompactResults(b.n, b.device, width=2))
+    torch.cuda.synchronize(b.device)
+    bench.dump_outputs(str(tmp_path), opt, b, out, c, 0, max_sample=2000)
+    got = {f[:-4]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    idx = got["sample_index"].astype(np.int64)
+    assert len(idx) == 2000 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < b.n
+    ref = out.host(b.n)[idx]
+    words = c.words[:b.n].cpu().numpy().view(np.uint16)[idx]
+    assert int(got["escape_count"][0]) == int(c.count.item()) > 100
+    assert ((words & 0x7F) == N.R16_ESCAPE).sum() > 10          # the sample holds escaped words
+    assert np.array_equal(got["compact_words"], words.astype(np.float32))
+    for k, f in enumerate(("best_x", "dist", "ov", "n_ties", "info")):
+        assert np.array_equal(got["results"][:, k], ref[f].astype(np.float32)), f
+
+
 def _bench(gpus, extra):
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--workload", "hg19",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra"] + extra,
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"] + extra,
                        env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
