@@ -180,7 +180,9 @@ __device__ __forceinline__ uint32_t decode(Bits &b, const uint32_t *fast, const 
 
 // the canonical code of lens[0, n) (RFC 1951 3.2.2): the fast table's entries for codes of up to F
 // bits (each lane fills its own symbols'), codes per length (cnt, and in cnt_v: lane l holds the
-// count of length l), the symbols in canonical order (sym); false if over-subscribed
+// count of length l), the symbols in canonical order (sym); false if over-subscribed, or incomplete
+// other than by having no symbol at all or a single codeword of length 1 (what libdeflate accepts of
+// every code and zlib of these two; a codeword such a code lacks is refused when it comes)
 template <int F>
 __device__ bool build(const uint8_t *lens, int n, uint32_t *fast, uint32_t *cnt, uint16_t *sym, Table t, int lane,
                       CodeV &cv) {
@@ -212,9 +214,10 @@ __device__ bool build(const uint8_t *lens, int n, uint32_t *fast, uint32_t *cnt,
         }
         idx += nl;
     }
-    if (left < 0) {                            // over-subscribed (once negative, left only falls)
-        __syncthreads();
-        return false;
+    const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)cnt_v, 1);
+    if (left < 0 || (left > 0 && idx > n1)) {  // over-subscribed (once negative, left only falls), or
+        __syncthreads();                       // incomplete with more than the one 1-bit codeword
+        return false;                          // (scalar: left, idx and n1 come from readlanes)
     }
     for (int base = 0; base < n; base += 64) {
         const int s = base + lane;
@@ -365,11 +368,12 @@ __global__ __launch_bounds__(64) void inflate_kernel(const uint8_t *__restrict__
         }
         if (type == 3) { st = INF_BAD_TYPE; break; }
         if (type == 1) {                        // fixed codes (RFC 1951 3.2.6)
-            for (int s = lane; s < 288 + 30; s += 64)
+            // (32 distance codes, so that the code is complete: meaning() marks 30 and 31 bad)
+            for (int s = lane; s < 288 + 32; s += 64)
                 L.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5);
             __syncthreads();
             if (!build<kLitBits>(L.lens, 288, L.lfast, L.cnt, L.lsym, T_LIT, lane, lcv) ||
-                !build<kDistBits>(L.lens + 288, 30, L.dfast, L.cnt, L.dsym, T_DIST, lane, dcv)) {
+                !build<kDistBits>(L.lens + 288, 32, L.dfast, L.cnt, L.dsym, T_DIST, lane, dcv)) {
                 st = INF_BAD_LITCODE;
                 break;
             }

@@ -1844,8 +1844,25 @@ extern "C" int fc2_ingest_open(const char *path, int is_bam, fc2_ingest **out) {
         return fc2::fail(FC2_E_IO, e);
     }
     pre.resize(got);
+    if (got == 18 && pre[0] == 0x1f && pre[1] == 0x8b && pre[2] == 8 && (pre[3] & 4)) {
+        // a gzip extra field longer than BGZF's own 'BC' subfield (other subfields before it): the
+        // whole field is read before the stream is taken for BGZF or not
+        const size_t want = 12 + (size_t)(pre[10] | (pre[11] << 8));
+        if (want > 18) {
+            pre.resize(want);
+            size_t more = 0;
+            if (!read_full(fd, pre.data() + 18, want - 18, more)) {
+                const std::string e = std::string("read error: ") + strerror(errno);
+                close(fd);
+                delete h;
+                return fc2::fail(FC2_E_IO, e);
+            }
+            got = 18 + more;
+            pre.resize(got);
+        }
+    }
     if (got >= 2 && pre[0] == 0x1f && pre[1] == 0x8b) {
-        if (got == 18 && bgzf_block_size(pre.data(), got) != 0) {
+        if (got >= 18 && bgzf_block_size(pre.data(), got) != 0) {
             // BGZF (BAM, or bgzip'ed SAM): blocks inflated in parallel, one batch ahead
             h->src = fc2_ingest::SRC_BGZF;
             h->bgzf = true;

@@ -65,3 +65,64 @@ def _first_diff(gpu, orc, m, k, label):
     i = int(bad[0])
     return "%s field %s differs at pair %d: gpu=%s oracle=%s (gpu n_ties=%s x=%s; oracle n_ties=%s x=%s)" % (
         label, k, i, gpu[k][i], orc[k][i], gpu["n_ties"][i], gpu["x"][i], orc["n_ties"][i], orc["x"][i])
+
+
+# ---- the GPU inflater (csrc/fc2_inflate.hip) through its C entry point -----------------------------
+SLOT = 65536                                     # a block's output slot (the BGZF ISIZE limit)
+
+
+def _inflate_pattern(n):
+    """What the output buffer holds before a launch (byte i of the allocation)."""
+    return ((np.arange(n, dtype=np.int64) * 197 + 91) & 255).astype(np.uint8)
+
+
+def inflate_launch(payloads, sizes, crcs=None):
+    """fc2_bgzf_inflate_launch over payloads (raw DEFLATE, packed back to back at every byte
+    alignment, so that a block's last word holds its neighbour's bytes) claimed to hold sizes bytes
+    (with CRC-32s crcs, if given).  The output buffer is pre-filled with _inflate_pattern and has one
+    guard slot before the first block's slot and one after the last: (the whole buffer, status)."""
+    import ctypes
+    import torch
+    n = len(payloads)
+    off, buf = [], bytearray()
+    rng = np.random.default_rng(len(payloads))
+    for p in payloads:
+        buf += bytes(int(rng.integers(0, 4)))          # payloads at every byte alignment
+        off.append(len(buf))
+        buf += p
+    buf += bytes(64)                                    # readable past every payload
+    dev = torch.device("cuda:0")
+    src = torch.tensor(np.frombuffer(bytes(buf), np.uint8), device=dev)
+    o = torch.tensor(np.array(off, np.uint32).view(np.int32), device=dev)
+    ln = torch.tensor(np.array([len(p) for p in payloads], np.uint32).view(np.int32), device=dev)
+    sz = torch.tensor(np.array(sizes, np.uint32).view(np.int32), device=dev)
+    cr = None if crcs is None else torch.tensor(np.array(crcs, np.uint32).view(np.int32), device=dev)
+    dst = torch.tensor(_inflate_pattern((max(1, n) + 2) * SLOT), device=dev)
+    st = torch.full((max(1, n),), -1, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    N.check(N.lib().fc2_bgzf_inflate_launch(src.data_ptr(), o.data_ptr(), ln.data_ptr(), sz.data_ptr(),
+                                            None if cr is None else cr.data_ptr(), dst.data_ptr() + SLOT, st.data_ptr(),
+                                            n, ctypes.c_void_p(stream)))
+    torch.cuda.synchronize(dev)
+    return dst.cpu().numpy(), st.cpu().numpy()[:n]
+
+
+def inflate_run(payloads, sizes, crcs=None, contained=False):
+    """The kernel over payloads claimed to hold sizes bytes (with CRC-32s crcs, if given): (outputs,
+    status).  With `contained`, also asserted: every block, inflated or refused, wrote only inside
+    [its slot, its slot + its claimed size rounded up to 16) -- the kernel's last row stores whole
+    16-byte pieces -- and nothing in a slot that is not its own, the two guard slots included."""
+    d, st = inflate_launch(payloads, sizes, crcs)
+    n = len(payloads)
+    if contained:
+        clean = d == _inflate_pattern(len(d))
+        for i in range(n):
+            a = (i + 1) * SLOT
+            own = min(SLOT, (sizes[i] + 15) // 16 * 16) if sizes[i] <= SLOT else 0
+            bad = np.nonzero(~clean[a + own:a + SLOT])[0]
+            assert len(bad) == 0, "block %d (status %d, size %d) wrote at byte %d of its slot" % (
+                i, st[i], sizes[i], own + int(bad[0]))
+        assert clean[:SLOT].all() and clean[(max(1, n) + 1) * SLOT:].all(), "a guard slot was written"
+        if n == 0:
+            assert clean.all()
+    return [d[(i + 1) * SLOT:(i + 1) * SLOT + sizes[i]].tobytes() for i in range(n)], st

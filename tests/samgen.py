@@ -56,17 +56,22 @@ _SEQ_CODE = {c: i for i, c in enumerate("=ACMGRSVTWYHKDBN")}
 _OPS = {c: i for i, c in enumerate("MIDNSHP=X")}
 
 
-def bgzf_compress(data: bytes, block: int = 65280, level: int = 6) -> bytes:
+def bgzf_compress(data: bytes, block: int = 65280, level: int = 6, deflate=None, extra: bytes = b"") -> bytes:
     """BGZF (SAM/BAM spec 4.1): gzip members of <= 64 KiB, compressed size in a 'BC' extra
-    field, followed by the 28-byte empty EOF block."""
+    field, followed by the 28-byte empty EOF block.  ``deflate`` (bytes -> raw DEFLATE) replaces
+    zlib at ``level``; ``extra`` holds further gzip extra subfields, placed before 'BC'."""
     import zlib
     out = bytearray()
     for k in range(0, len(data), block):
         chunk = data[k:k + block]
-        co = zlib.compressobj(level, zlib.DEFLATED, -15)
-        cdata = co.compress(chunk) + co.flush()
-        bsize = 18 + len(cdata) + 8
-        out += b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize - 1)
+        if deflate is None:
+            co = zlib.compressobj(level, zlib.DEFLATED, -15)
+            cdata = co.compress(chunk) + co.flush()
+        else:
+            cdata = deflate(chunk)
+        bsize = 18 + len(extra) + len(cdata) + 8
+        out += b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff" + struct.pack("<H", 6 + len(extra)) + extra + \
+            b"BC\x02\x00" + struct.pack("<H", bsize - 1)
         out += cdata + struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk))
     out += bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
     return bytes(out)

@@ -10,46 +10,15 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from gpu_helpers import SLOT, inflate_run as _run
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-SLOT = 65536
 
 
 def _deflate(data: bytes, level=6, strategy=zlib.Z_DEFAULT_STRATEGY) -> bytes:
     c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
     return c.compress(data) + c.flush()
-
-
-def _run(payloads, sizes, crcs=None):
-    """The kernel over payloads (raw DEFLATE) claimed to hold sizes bytes (with CRC-32s crcs, if
-    given): (outputs, status)."""
-    import ctypes
-    from find_circ2_amd import _native as N
-    n = len(payloads)
-    off, buf = [], bytearray()
-    rng = np.random.default_rng(len(payloads))
-    for p in payloads:
-        buf += bytes(int(rng.integers(0, 4)))          # payloads at every byte alignment
-        off.append(len(buf))
-        buf += p
-    buf += bytes(64)                                    # readable past every payload
-    dev = torch.device("cuda:0")
-    src = torch.tensor(np.frombuffer(bytes(buf), np.uint8), device=dev)
-    o = torch.tensor(np.array(off, np.uint32).view(np.int32), device=dev)
-    ln = torch.tensor(np.array([len(p) for p in payloads], np.uint32).view(np.int32), device=dev)
-    sz = torch.tensor(np.array(sizes, np.uint32).view(np.int32), device=dev)
-    cr = None if crcs is None else torch.tensor(np.array(crcs, np.uint32).view(np.int32), device=dev)
-    dst = torch.zeros(max(1, n) * SLOT, dtype=torch.uint8, device=dev)
-    st = torch.full((max(1, n),), -1, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    N.check(N.lib().fc2_bgzf_inflate_launch(src.data_ptr(), o.data_ptr(), ln.data_ptr(), sz.data_ptr(),
-                                            None if cr is None else cr.data_ptr(), dst.data_ptr(), st.data_ptr(), n,
-                                            ctypes.c_void_p(stream)))
-    torch.cuda.synchronize(dev)
-    d = dst.cpu().numpy()
-    return [d[i * SLOT:i * SLOT + sizes[i]].tobytes() for i in range(n)], st.cpu().numpy()[:n]
 
 
 def _samples():
@@ -207,6 +176,108 @@ def test_ingest_gpu_inflate_equals_cpu(tmp_path, monkeypatch, batch):
         ahead = min(16, int(batch)) + int(batch)
         assert gpu[2] == (max(0, n_blocks - ahead), 0), (bam, gpu[2], n_blocks)
         assert cpu[2] == (0, 0)
+
+
+def _block_spans(raw: bytes):
+    """(start, size) of every block of a BGZF file, its 'BC' subfield found among any others."""
+    out, pos = [], 0
+    while pos < len(raw):
+        xlen = raw[pos + 10] | (raw[pos + 11] << 8)
+        q = pos + 12
+        while raw[q:q + 2] != b"BC":
+            q += 4 + (raw[q + 2] | (raw[q + 3] << 8))
+            assert q < pos + 12 + xlen
+        bsize = (raw[q + 4] | (raw[q + 5] << 8)) + 1
+        out.append((pos, bsize))
+        pos += bsize
+    return out
+
+
+def _raw_rich_bam(tmp_path):
+    """The uncompressed BAM bytes of the rich SAM of _bams()."""
+    from samgen import sam_to_bam as py_sam_to_bam
+    from test_native_caller import _rich_sam
+    sam = str(tmp_path / "rich.sam")
+    _rich_sam(sam, 4000, seed=7)
+    raw = str(tmp_path / "raw.bam")
+    py_sam_to_bam(open(sam).read(), raw, compress="none")
+    return open(raw, "rb").read()
+
+
+@pytest.mark.parametrize("writer", ["libdeflate1", "libdeflate12", "extra_subfield"])
+def test_ingest_gpu_inflate_other_writers(tmp_path, monkeypatch, writer):
+    """BAMs as htslib built with libdeflate writes them (several DEFLATE blocks a BGZF block, levels 1
+    and 12, 0xff00-byte blocks), and one with a 5-byte extra subfield before 'BC' in every block: the
+    same fragments and counts as with the CPU inflate, every block after the read-ahead inflated on
+    the GPU and none retried on the CPU."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from samgen import bgzf_compress
+    from test_deflate_forge import LIBDEFLATE, libdeflate_deflate
+    monkeypatch.setenv("FC2_BGZF_BATCH", "3")
+    data = _raw_rich_bam(tmp_path)
+    if writer == "extra_subfield":
+        packed = bgzf_compress(data, block=0xff00, level=1, extra=b"XY\x01\x00\x5a")
+    else:
+        if LIBDEFLATE is None:
+            pytest.skip("libdeflate.so.0 does not load")
+        level = int(writer[len("libdeflate"):])
+        packed = bgzf_compress(data, block=0xff00, deflate=lambda chunk: libdeflate_deflate(chunk, level))
+    bam = str(tmp_path / (writer + ".bam"))
+    open(bam, "wb").write(packed)
+    cpu = _read_all(bam)
+    gpu = _read_all(bam, 0)
+    assert isinstance(cpu[0], list) and cpu[0], cpu
+    assert cpu[:2] == gpu[:2]
+    n_blocks = len(_block_spans(packed))
+    assert n_blocks > 10
+    assert gpu[2] == (n_blocks - (3 + 3), 0), (gpu[2], n_blocks)
+    assert cpu[2] == (0, 0)
+
+
+@pytest.mark.parametrize("form", ["dist_incomplete", "litlen_incomplete", "valid_15bit_trailing", "unused_codeword"])
+def test_ingest_gpu_inflate_forged_block(tmp_path, monkeypatch, form):
+    """The 10th block of a BAM (the GPU's) replaced by one carrying the same BAM bytes, CRC-32 and
+    ISIZE in a forged DEFLATE stream: an incomplete distance code and an incomplete literal/length
+    code (both CPU inflaters refuse them), 15-bit dynamic codes with bytes left over after the final
+    block (valid), and the unused codeword of a single 1-bit distance code (zlib refuses it,
+    libdeflate decodes the code's distance).  The GPU inflate gives the run the CPU inflate gives:
+    the same fragments and counts, or the same error."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from deflate_forge import Code, Forge, LenOnly, make_code
+    from samgen import bgzf_compress
+    from test_deflate_forge import D15, L15
+    monkeypatch.setenv("FC2_BGZF_BATCH", "4")
+    _, small, _ = _bams(tmp_path)
+    raw = open(small, "rb").read()
+    start, size = _block_spans(raw)[9]
+    chunk = zlib.decompress(raw[start + 18:start + size - 8], -15)
+    assert len(chunk) == 3000
+    if form == "dist_incomplete":
+        forged = bytes(Forge().dynamic(L15, [2, 2], list(chunk), True))
+    elif form == "litlen_incomplete":
+        forged = bytes(Forge().dynamic(L15[:285] + [0], D15, list(chunk), True))
+    elif form == "valid_15bit_trailing":
+        forged = bytes(Forge().dynamic(L15, D15, list(chunk), True).raw_bytes(b"left over"))
+    else:
+        k = next(i for i in range(1, len(chunk) - 3) if chunk[i - 1:i] * 3 == chunk[i:i + 3])
+        toks = list(chunk[:k]) + [LenOnly(3), Code(1, 1)] + list(chunk[k + 3:])
+        forged = bytes(Forge().dynamic(make_code(286, 9), [1], toks, True))
+    block = bgzf_compress(chunk, block=len(chunk), deflate=lambda _: forged)[:-28]
+    bam = str(tmp_path / (form + ".bam"))
+    open(bam, "wb").write(raw[:start] + block + raw[start + size:])
+    cpu, gpu = _read_all(bam), _read_all(bam, 0)
+    if cpu[2] is None:                                   # refused: the same error
+        assert "corrupt BGZF block" in cpu[1], cpu
+        assert gpu == cpu
+    else:
+        assert isinstance(cpu[0], list) and cpu[0] and cpu[:2] == gpu[:2]
+        assert cpu[:2] == _read_all(small)[:2]
+    if form == "valid_15bit_trailing":
+        assert cpu[2] == (0, 0) and gpu[2] is not None and gpu[2][0] > 0 and gpu[2][1] == 0, (cpu[2], gpu[2])
+    if form in ("dist_incomplete", "litlen_incomplete"):
+        assert cpu[2] is None
 
 
 def test_ingest_gpu_inflate_from_a_threshold(tmp_path, monkeypatch):
