@@ -158,7 +158,8 @@ EXPORTED = [
     # include/fc2_caller.h
     "fc2_caller_open", "fc2_caller_set_genome", "fc2_caller_inflate_counts", "fc2_caller_ingest", "fc2_caller_close", "fc2_caller_next",
     "fc2_caller_submit", "fc2_caller_submit_compact", "fc2_caller_submit_long", "fc2_caller_queued", "fc2_caller_take", "fc2_caller_rows", "fc2_caller_write_rows", "fc2_caller_counter", "fc2_caller_stats",
-    "fc2_caller_set_reads_gz", "fc2_caller_close_reads",
+    "fc2_caller_set_reads_gz", "fc2_caller_close_reads", "fc2_caller_set_reads_gz_device", "fc2_caller_reads_gz_counts",
+    "fc2_deflate_launch", "fc2_deflate_scratch_bytes", "fc2_gpu_gzip", "fc2_gpu_gzip_bound", "fc2_caller_set_reads_gz_device_tuning",
     # include/fc2_ctx.h
     "fc2_ctx_create", "fc2_ctx_create_sibling", "fc2_ctx_destroy", "fc2_ctx_genome_load", "fc2_ctx_genome_view", "fc2_ctx_scan_async",
     "fc2_ctx_sync", "fc2_ctx_scan_long", "fc2_ctx_stream", "fc2_ctx_last_error",
@@ -197,7 +198,8 @@ _lib = None
 def build(force: bool = False) -> str:
     srcdir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(srcdir, f) for f in ("fc2_kernels.hip", "fc2_scan32.hip", "fc2_reorder.hip", "fc2_inflate.hip",
-                                              "fc2_scan32.h",
+                                              "fc2_deflate.hip", "fc2_deflate_gpu.hip", "fc2_deflate_gpu.h", "fc2_devcrc.h",
+                                              "fc2_gzpieces.h", "fc2_scan32.h",
                                               "fc2_host.cpp", "fc2_ingest.cpp", "fc2_ingest_impl.h", "fc2_caller.cpp",
                                               "fc2_bamout.cpp", "fc2_bamout.h", "fc2_ctx.cpp", "fc2_hostmem.h",
                                               "fc2_common.h", "Makefile")]
@@ -291,6 +293,13 @@ def lib() -> ctypes.CDLL:
         "fc2_caller_take": (ctypes.c_int, [vp, ctypes.c_int, P(ctypes.c_void_p), P(u64)]),
         "fc2_caller_set_reads_gz": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, u64]),
         "fc2_caller_close_reads": (ctypes.c_int, [vp]),
+        "fc2_caller_set_reads_gz_device": (ctypes.c_int, [vp, ctypes.c_int]),
+        "fc2_caller_reads_gz_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
+        "fc2_deflate_launch": (ctypes.c_int, [vp, u64, u32, vp, u32, vp, vp, vp, vp]),
+        "fc2_deflate_scratch_bytes": (u64, [u64, u32]),
+        "fc2_gpu_gzip": (ctypes.c_int, [ctypes.c_int, vp, u64, u32, vp, u64, P(u64)]),
+        "fc2_gpu_gzip_bound": (u64, [u64, u32]),
+        "fc2_caller_set_reads_gz_device_tuning": (ctypes.c_int, [vp, u32, ctypes.c_double]),
         "fc2_caller_rows": (ctypes.c_int, [vp, ctypes.c_int, P(ctypes.c_void_p), P(u64)]),
         "fc2_caller_write_rows": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, P(u64)]),
         "fc2_caller_counter": (ctypes.c_int, [vp, ctypes.c_int, P(ctypes.c_char_p), P(ctypes.c_double)]),

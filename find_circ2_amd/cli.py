@@ -283,6 +283,17 @@ def _inflate_device(options):
     return device_index(options.device), (0 if env in ("1", "2") else GPU_INFLATE_AFTER)
 
 
+def _gzip_device(options):
+    """spliced_reads.fastq.gz compressed on the GPU: only with FC2_GPU_GZIP=1, on the first of
+    the run's devices, in tiles of FC2_GPU_GZIP_TILE bytes (32768), waiting at most
+    FC2_GPU_GZIP_TIMEOUT_S seconds (60) for the device.  Anything but 1: {}, the worker threads compress."""
+    if os.environ.get("FC2_GPU_GZIP") != "1":
+        return {}
+    from .ctxpipe import device_index
+    return dict(gzip_device=device_index(options.device), gzip_tile=int(os.environ.get("FC2_GPU_GZIP_TILE") or 0),
+                gzip_timeout_s=float(os.environ.get("FC2_GPU_GZIP_TIMEOUT_S") or 0))
+
+
 def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory, genome, bam_path="",
                        genome_eval=None, startup=None) -> int:
     """The read loop in C++ (include/fc2_caller.h); only the breakpoint search is called from here."""
@@ -306,7 +317,8 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                       known_circ=options.known_circ, known_lin=options.known_lin, bam_out=bam_path,
                       reads_gz=reads_gz,
                       **(dict(zip(("inflate_device", "inflate_after"), _inflate_device(options)))
-                         if genome_eval is not None else {}))
+                         if genome_eval is not None else {}),
+                      **(_gzip_device(options) if genome_eval is not None and reads_gz else {}))
     try:
         try:
             n_kc, n_kl = nc.open()
@@ -357,6 +369,9 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                            siblings_s=getattr(evaluate, "siblings_s", 0.0), read_loop_s=seconds,
                            genome_wait_s=getattr(evaluate, "wait_s", 0.0), tables_s=time.time() - t_rows)
             startup.update(zip(("inflate_gpu_blocks", "inflate_cpu_blocks"), nc.inflate_counts()))
+            if nc.gzip_device is not None:      # the last pieces are compressed as the file is finished
+                nc.finish_reads()
+            startup.update(zip(("gzip_gpu_pieces", "gzip_cpu_pieces"), nc.reads_gz_counts()))
             logger.info("process phases: " + ", ".join("%s=%.3f" % kv for kv in startup.items()) +
                         ", process_age_s=%.3f, numpy_loaded=%d, torch_loaded=%d"
                         % (process_age(), "numpy" in sys.modules, "torch" in sys.modules))

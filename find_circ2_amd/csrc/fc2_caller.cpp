@@ -885,6 +885,9 @@ struct fc2_caller {
     std::string rows_text;
     std::vector<std::pair<std::string, double>> counters_snapshot;
     uint64_t n_pairs = 0;
+    bool submitted = false;                     // fc2_caller_submit was called (fc2_caller_set_reads_gz_device: before)
+    uint32_t gz_tile = 0;                       // fc2_caller_set_reads_gz_device_tuning (0: the defaults)
+    double gz_timeout_s = 0;
     uint64_t n_chunks = 0;                      // chunks formed (next side)
 };
 
@@ -2506,6 +2509,7 @@ extern "C" int fc2_caller_queued(fc2_caller *h) {
 extern "C" int fc2_caller_submit(fc2_caller *h, const fc2_result *results, const uint64_t *tiemask, uint32_t tw,
                                  uint64_t stride) {
     if (!h) return fc2::fail(FC2_E_PARAM, "fc2_caller_submit: null argument");
+    h->submitted = true;
     {
         std::lock_guard<std::mutex> lk(h->qmu);
         if (h->queued.empty())
@@ -2690,6 +2694,32 @@ extern "C" int fc2_caller_set_reads_gz(fc2_caller *h, const char *path, int leve
     std::string err;
     if (!h->reads_gz.open(path, level, threads, piece ? (size_t)piece : size_t(4) << 20, err))
         return fc2::fail(FC2_E_IO, err);
+    return FC2_OK;
+}
+
+extern "C" int fc2_caller_set_reads_gz_device(fc2_caller *h, int device) {
+    if (!h || device < 0) return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: bad arguments");
+    if (!h->reads_gz.is_open() || h->reads_gz.device_mode() || h->submitted)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: call once, after fc2_caller_set_reads_gz and before "
+                                      "the first fc2_caller_submit");
+    std::string err;
+    if (!h->reads_gz.set_device(device, h->gz_tile, h->gz_timeout_s, err)) return fc2::fail(FC2_E_HIP, "fc2_caller_set_reads_gz_device: " + err);
+    return FC2_OK;
+}
+
+extern "C" int fc2_caller_set_reads_gz_device_tuning(fc2_caller *h, uint32_t tile, double timeout_s) {
+    if (!h || tile > 65536 || !(timeout_s >= 0))
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_tuning: null handle, tile over 65536 or negative time");
+    if (h->reads_gz.device_mode())
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_tuning: call before fc2_caller_set_reads_gz_device");
+    h->gz_tile = tile;
+    h->gz_timeout_s = timeout_s;
+    return FC2_OK;
+}
+
+extern "C" int fc2_caller_reads_gz_counts(const fc2_caller *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_caller_reads_gz_counts: null argument");
+    h->reads_gz.counts(gpu_pieces, cpu_pieces);
     return FC2_OK;
 }
 

@@ -1,5 +1,7 @@
 // fc2_deflate.h -- whole-buffer DEFLATE for the loop's hot (de)compression: BGZF blocks inflated
-// and CRC-checked (fc2_ingest.cpp), the gzip members of spliced_reads.fastq.gz (fc2_gzpieces.h).
+// and CRC-checked (fc2_ingest.cpp), the gzip members of spliced_reads.fastq.gz (fc2_gzpieces.h) --
+// on the CPU: the worker threads' side of that file.  Its device mode compresses on the GPU instead
+// (fc2_deflate.hip, fc2_deflate_gpu.h) and comes here only for the pieces the device hands back.
 // libdeflate (the image's libdeflate.so.0, 1.10; loaded at run time, its header is not installed,
 // so the few entry points are declared here) inflates about twice and checks CRC-32 many times
 // faster than zlib; zlib stays the fallback when the library is absent, and FC2_LIBDEFLATE=0

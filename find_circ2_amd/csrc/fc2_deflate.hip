@@ -1,0 +1,614 @@
+// fc2_deflate.hip -- DEFLATE compression on the GPU: the gzip members of spliced_reads.fastq.gz
+// (fc2_gzpieces.h's device mode, fc2_deflate_gpu.hip), the mirror image of fc2_inflate.hip.
+//
+// The text is cut into tiles of at most 64 KiB; a tile never refers to bytes before its own start,
+// so tiles are independent: one wavefront per tile, no waits between workgroups.  Each tile becomes
+// one complete raw DEFLATE stream (RFC 1951) -- a single dynamic-Huffman block, or stored block(s)
+// when that would not be smaller -- with the gzip CRC-32 of its input beside it, so the host only
+// wraps it in a gzip header and trailer, and the project's own inflater can read it back.
+//
+// The tile is held whole in LDS.  Pass 1 (matches): 64 consecutive positions a step, one per lane;
+// a hash of the next 4 bytes indexes a table of last positions (read first, then updated with an LDS
+// atomicMax of the position, so the table does not depend on the order the lanes get there); the
+// candidate is compared 4 bytes at a time; a match is kept if it should cost less than its bytes as
+// literals (the tile's byte entropy, from a histogram taken while the tile is loaded, against the
+// length and distance codes' sizes); overlaps inside the 64 positions are resolved greedily in scalar
+// code over the ballot of the lanes that found one.  The tokens go to a per-tile scratch in global
+// memory (4 bytes each; they do not fit in LDS beside the tile) and into the two symbol histograms.
+// The Huffman codes (lengths <= 15, zlib's overflow repair; always complete: a code with fewer than
+// two symbols is padded with dummy ones as zlib does) are built with the symbols ranked in parallel
+// and the tree made by one lane, in the hash table's LDS, free by then.  Pass 2 (emission): 64 tokens a
+// step, a prefix sum of their bit counts over the lanes, each lane ORs its bits into a staging
+// buffer in LDS (atomicOr on 32-bit words) that is laid out with the destination's alignment, so it
+// is flushed to HBM in whole aligned 16-byte pieces; only the first and last pieces of a stream are
+// stored byte by byte, and nothing outside [slot, slot + out_len) is written.
+//
+// LDS: 22540 B beside the tile (hash table 16 KiB, staging 3 KiB, histograms, codes): 55324 B with a
+// tile of 32 KiB -- two workgroups a CU of 160 KiB -- and 88092 B with one of 64 KiB: one a CU.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <atomic>
+#include <string>
+
+#include "../../include/fc2_caller.h"
+#include "fc2_common.h"
+#include "fc2_devcrc.h"
+
+namespace {
+
+constexpr uint32_t kTileMax = 65536;
+constexpr int kHashBits = 12;
+constexpr uint32_t kMinMatch = 4, kMaxMatch = 258, kMaxDist = 32768;
+constexpr uint32_t kStageWords = 768;          // 3 KiB: flushed once 2 KiB are full; a step adds < 400 bytes
+constexpr uint32_t kStageFlush = 2048;
+constexpr uint32_t kTokMatch = 0x80000000u;    // token: a literal's byte, or this | (len - 3) << 16 | (dist - 1)
+constexpr uint32_t kFailed = 0xFFFFFFFFu;      // out_len of a tile the kernel gave up on (the host compresses it)
+
+__constant__ uint8_t kDClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+struct Lds {
+    uint32_t htab[1 << kHashBits];             // last position + 1 per hash; then the code builder's workspace
+    uint32_t stage[kStageWords];
+    uint32_t lfreq[288], dfreq[32], cfreq[20]; // (lfreq: the bytes' histogram first, then literal/length symbols)
+    uint32_t blc[16];
+    uint16_t lcode[288], dcode[32], ccode[20]; // codewords, bit-reversed: as they go into the stream
+    uint16_t rle[320];                         // the code lengths' run-length form: symbol | extra << 8
+    uint8_t llen[288], dlen[32], clen[20];
+    uint32_t tile[1];                          // the tile's bytes and 16 bytes of zeros (dynamic)
+};
+
+// the code builder's workspace inside htab (m <= 286 symbols in use: 2 m - 1 nodes)
+struct Work {
+    uint32_t w[576];
+    uint16_t par[576], sorted[288];
+    uint8_t dep[576];
+};
+static_assert(sizeof(Work) <= sizeof(uint32_t) << kHashBits, "the code builder works in the hash table");
+
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// 4 bytes at any byte offset of the tile (little-endian), from two aligned words
+__device__ __forceinline__ uint32_t load32u(const uint32_t *t, uint32_t p) {
+    const uint32_t k = p >> 2;
+    const uint64_t v = (uint64_t)t[k] | ((uint64_t)t[k + 1] << 32);
+    return (uint32_t)(v >> ((p & 3u) * 8u));
+}
+
+// 16 log2(x), x >= 1: the mantissa's top four bits stand for the fraction
+__device__ __forceinline__ uint32_t log2x16(uint32_t x) {
+    const uint32_t m = 31u - (uint32_t)__clz((int)x);
+    return 16u * m + (((x << (31u - m)) >> 27) & 15u);
+}
+
+// length l = len - 3 (0..255): its symbol, extra-bit count and extra bits (RFC 1951 3.2.5)
+__device__ __forceinline__ void len_sym(uint32_t l, uint32_t &sym, uint32_t &eb, uint32_t &ev) {
+    if (l < 8u) { sym = 257u + l; eb = 0; ev = 0; return; }
+    if (l == 255u) { sym = 285u; eb = 0; ev = 0; return; }
+    eb = 29u - (uint32_t)__clz((int)l);
+    sym = 261u + 4u * eb + ((l >> eb) & 3u);
+    ev = l & ((1u << eb) - 1u);
+}
+// distance d = dist - 1 (0..32767)
+__device__ __forceinline__ void dist_sym(uint32_t d, uint32_t &sym, uint32_t &eb, uint32_t &ev) {
+    if (d < 4u) { sym = d; eb = 0; ev = 0; return; }
+    const uint32_t m = 31u - (uint32_t)__clz((int)d);
+    eb = m - 1u;
+    sym = 2u * m + ((d >> eb) & 1u);
+    ev = d & ((1u << eb) - 1u);
+}
+
+// Code lengths <= maxbits for the n symbols' frequencies (a Huffman code, repaired as zlib's
+// gen_bitlen does when the tree is deeper), and the bit-reversed canonical codewords.  A code with
+// fewer than two symbols in use gets dummy ones (symbols 0 / 1, frequency 1; zlib's build_tree), so
+// it is always complete.  False if the lengths do not add up to a complete code (not expected).
+__device__ bool build_code(uint32_t *freq, int n, int maxbits, uint8_t *lens, uint16_t *code, uint32_t *blc, Work &W,
+                           int lane) {
+    __syncthreads();
+    uint32_t used = 0;
+    for (int b = 0; b < n; b += 64) {
+        const int s = b + lane;
+        used += (uint32_t)__popcll(__ballot(s < n && freq[s] != 0));
+    }
+    if (used < 2u && lane == 0) {
+        if (freq[0] == 0) { freq[0] = 1; ++used; }
+        if (used < 2u) freq[1] = 1;            // (freq[1] is 0 here: otherwise two were in use)
+    }
+    used = used < 2u ? 2u : used;
+    const int m = (int)used;
+    for (int s = lane; s < n; s += 64) lens[s] = 0;
+    if (lane < 16) blc[lane] = 0;
+    __syncthreads();
+    // the symbols in use in ascending order of (frequency, symbol): each lane ranks its own
+    for (int s = lane; s < n; s += 64) {
+        const uint32_t f = freq[s];
+        if (!f) continue;
+        uint32_t r = 0;
+        for (int j = 0; j < n; ++j) {
+            const uint32_t g = freq[j];
+            r += (g != 0 && (g < f || (g == f && j < s))) ? 1u : 0u;
+        }
+        W.sorted[r] = (uint16_t)s;
+        W.w[r] = f;
+    }
+    __syncthreads();
+    bool ok = true;
+    if (lane == 0) {
+        // leaves 0..m-1 in order, inner nodes m..2m-2 in the order they are made (their weights rise too)
+        int i = 0, j = m;
+        for (int k = m; k < 2 * m - 1; ++k) {
+            uint32_t sum = 0;
+            for (int t = 0; t < 2; ++t) {
+                int pick;
+                if (i < m && (j >= k || W.w[i] <= W.w[j])) pick = i++;
+                else pick = j++;
+                sum += W.w[pick];
+                W.par[pick] = (uint16_t)k;
+            }
+            W.w[k] = sum;
+        }
+        // depths from the root down, cut at maxbits (overflow counts the nodes cut)
+        int overflow = 0;
+        W.dep[2 * m - 2] = 0;
+        for (int k = 2 * m - 3; k >= 0; --k) {
+            int d = (int)W.dep[W.par[k]] + 1;
+            if (d > maxbits) { d = maxbits; ++overflow; }
+            W.dep[k] = (uint8_t)d;
+            if (k < m) ++blc[d];
+        }
+        while (overflow > 0) {                  // move a leaf down the tree, a leaf of the last level up
+            int bits = maxbits - 1;
+            while (bits > 0 && blc[bits] == 0) --bits;
+            if (bits == 0) break;
+            --blc[bits];
+            blc[bits + 1] += 2;
+            --blc[maxbits];
+            overflow -= 2;
+        }
+        uint32_t kraft = 0, total = 0;
+        for (int b = 1; b <= maxbits; ++b) {
+            kraft += blc[b] << (maxbits - b);
+            total += blc[b];
+        }
+        ok = kraft == (1u << maxbits) && total == (uint32_t)m;
+        if (ok) {
+            int idx = 0;                        // the rarest symbols get the longest codewords
+            for (int b = maxbits; b >= 1; --b)
+                for (uint32_t c = 0; c < blc[b]; ++c) lens[W.sorted[idx++]] = (uint8_t)b;
+            uint32_t next[16];
+            uint32_t c = 0;
+            next[0] = 0;
+            for (int b = 1; b <= maxbits; ++b) {
+                c = (c + (b > 1 ? blc[b - 1] : 0u)) << 1;
+                next[b] = c;
+            }
+            for (int s = 0; s < n; ++s) {
+                const uint32_t l = lens[s];
+                code[s] = l ? (uint16_t)(__builtin_bitreverse32(next[l]++) >> (32u - l)) : (uint16_t)0;
+            }
+        }
+    }
+    ok = uni(ok ? 1u : 0u) != 0;
+    __syncthreads();
+    return ok;
+}
+
+// the stream's bytes as they are staged: coordinate c = the destination's low four address bits + the
+// byte's index in the stream, so that staged 16-byte pieces are aligned 16-byte pieces of HBM
+struct Out {
+    uint8_t *base;                             // slot - a (16-byte aligned; bytes before `a` are never touched)
+    uint32_t a;                                // the first coordinate
+    uint32_t limit;                            // a + FC2_DEFLATE_TILE_BOUND(tile): no store at or past it
+    uint32_t stage0;                           // coordinate of stage[0]'s first byte (a multiple of 16)
+    uint64_t bit;                              // the next bit's position, 8 a + bits so far
+    bool over;
+};
+
+// staged coordinates [stage0, upto) to HBM; bytes outside [a, min(upto, limit)) are not stored
+__device__ void store_pieces(const Lds &L, Out &o, uint32_t upto, int lane) {
+    const uint32_t end = upto < o.limit ? upto : o.limit;
+    if (upto > o.limit) o.over = true;
+    for (uint32_t c0 = o.stage0 + 16u * (uint32_t)lane; c0 < end; c0 += 1024u) {
+        const uint32_t wi = (c0 - o.stage0) >> 2;
+        const uint4 v = make_uint4(L.stage[wi], L.stage[wi + 1], L.stage[wi + 2], L.stage[wi + 3]);
+        if (c0 >= o.a && c0 + 16u <= end) {
+            *reinterpret_cast<uint4 *>(o.base + c0) = v;
+        } else {
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            const uint32_t lo = c0 > o.a ? c0 : o.a, hi = c0 + 16u < end ? c0 + 16u : end;
+            for (uint32_t c = lo; c < hi; ++c) o.base[c] = (uint8_t)(w[(c - c0) >> 2] >> (8u * (c & 3u)));
+        }
+    }
+}
+
+// whole staged 16-byte pieces to HBM once 2 KiB are full; the unfinished piece moves to the front
+__device__ void flush_stage(Lds &L, Out &o, int lane) {
+    const uint32_t bytes = (uint32_t)(o.bit >> 3);       // whole bytes so far, as a coordinate
+    if (bytes - o.stage0 < kStageFlush) return;
+    __syncthreads();
+    const uint32_t upto = bytes & ~15u;
+    store_pieces(L, o, upto, lane);
+    const uint32_t wi = (upto - o.stage0) >> 2;
+    const uint32_t keep = lane < 8 ? L.stage[wi + (uint32_t)lane] : 0u;   // (< 16 bytes and a part of one are left)
+    __syncthreads();
+    for (uint32_t k = (uint32_t)lane; k < kStageWords; k += 64) L.stage[k] = 0;
+    __syncthreads();
+    if (lane < 8) L.stage[lane] = keep;
+    o.stage0 = upto;
+    __syncthreads();
+}
+
+// nb <= 57 bits of v at the stream's bit position `at` (a position, not a coordinate in the stage)
+__device__ __forceinline__ void or_bits(Lds &L, const Out &o, uint64_t at, uint64_t v, uint32_t nb) {
+    if (!nb) return;
+    const uint32_t rel = (uint32_t)(at - (uint64_t)o.stage0 * 8u);
+    const uint32_t wi = rel >> 5, sh = rel & 31u;
+    const uint32_t w0 = (uint32_t)(v << sh), w1 = (uint32_t)((v << sh) >> 32);
+    const uint32_t w2 = sh ? (uint32_t)(v >> (64u - sh)) : 0u;
+    if (wi + 2u >= kStageWords) return;        // (cannot happen: a flush leaves a KiB free)
+    if (w0) atomicOr(&L.stage[wi], w0);
+    if (w1) atomicOr(&L.stage[wi + 1], w1);
+    if (w2) atomicOr(&L.stage[wi + 2], w2);
+}
+
+// one lane's bit writer (the block header)
+__device__ __forceinline__ void put(Lds &L, Out &o, uint32_t v, uint32_t nb) {
+    or_bits(L, o, o.bit, (uint64_t)v, nb);
+    o.bit += nb;
+}
+
+__global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__ src, uint64_t n_bytes, uint32_t tile,
+                                                     uint8_t *__restrict__ dst, uint32_t stride,
+                                                     uint32_t *__restrict__ out_len, uint32_t *__restrict__ crc,
+                                                     uint32_t *__restrict__ scratch) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    Lds &L = *reinterpret_cast<Lds *>(smem);
+    uint32_t *T = L.tile;
+    const uint32_t blk = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    const uint64_t start = (uint64_t)blk * tile;
+    if (start >= n_bytes) return;
+    const uint32_t n = (uint32_t)(n_bytes - start < (uint64_t)tile ? n_bytes - start : (uint64_t)tile);   // 1..65536
+    const uint8_t *in = src + start;
+    uint8_t *slot = dst + (uint64_t)blk * stride;
+    uint32_t *tok = scratch + start;           // n tokens at most
+
+    // ---- the tile into LDS, its bytes' histogram and its CRC-32 ---------------------------------
+    for (uint32_t k = (uint32_t)lane; k < (1u << kHashBits); k += 64) L.htab[k] = 0;
+    for (uint32_t k = (uint32_t)lane; k < kStageWords; k += 64) L.stage[k] = 0;
+    for (uint32_t k = (uint32_t)lane; k < 288u; k += 64) L.lfreq[k] = 0;
+    if (lane < 32) L.dfreq[lane] = 0;
+    if (lane < 20) L.cfreq[lane] = 0;
+    const uint32_t nw = (n + 3u) >> 2;         // words holding the tile; four more are zeroed
+    __syncthreads();
+    if (((uintptr_t)in & 15u) == 0) {
+        for (uint32_t b0 = 16u * (uint32_t)lane; b0 < n; b0 += 1024u) {
+            if (b0 + 16u <= n) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(in + b0);
+                T[b0 >> 2] = v.x; T[(b0 >> 2) + 1] = v.y; T[(b0 >> 2) + 2] = v.z; T[(b0 >> 2) + 3] = v.w;
+            } else {
+                for (uint32_t w = 0; w < 4u; ++w) {
+                    uint32_t v = 0;
+                    for (uint32_t i = 0; i < 4u; ++i) {
+                        const uint32_t p = b0 + 4u * w + i;
+                        if (p < n) v |= (uint32_t)in[p] << (8u * i);
+                    }
+                    T[(b0 >> 2) + w] = v;      // (words up to nw + 3 at most: inside the 16 bytes of padding)
+                }
+            }
+        }
+    } else {
+        for (uint32_t k = (uint32_t)lane; k < nw; k += 64) {
+            uint32_t v = 0;
+            for (uint32_t i = 0; i < 4u; ++i) {
+                const uint32_t p = 4u * k + i;
+                if (p < n) v |= (uint32_t)in[p] << (8u * i);
+            }
+            T[k] = v;
+        }
+    }
+    __syncthreads();
+    if (lane < 4) T[nw + (uint32_t)lane] = 0;
+    __syncthreads();
+    for (uint32_t k = (uint32_t)lane; k < nw; k += 64) {
+        const uint32_t v = T[k];
+        for (uint32_t i = 0; i < 4u; ++i)
+            if (4u * k + i < n) atomicAdd(&L.lfreq[(v >> (8u * i)) & 255u], 1u);
+    }
+    uint32_t R = 0;                             // raw CRC, in rows of 1024 bytes as the inflater's
+    uint32_t done = 0;
+    for (; done + 1024u <= n; done += 1024u) {
+        const uint32_t k = (done >> 2) + 4u * (uint32_t)lane;
+        const uint32_t c = crc_word(crc_word(crc_word(crc_word(0u, T[k]), T[k + 1]), T[k + 2]), T[k + 3]);
+        R = multmodp(kX2n[13], R) ^ wave_fold(c);
+    }
+    for (; done < n; ++done) {                  // the last, short row byte by byte, on every lane alike
+        R ^= (T[done >> 2] >> (8u * (done & 3u))) & 255u;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) R = mulx(R);
+    }
+    const uint32_t tile_crc = R ^ multmodp(x8n(n), 0xFFFFFFFFu) ^ 0xFFFFFFFFu;
+    __syncthreads();
+
+    // what a literal costs on average, in 1/16 bit: the bytes' entropy, at least a bit each
+    uint32_t cost = 0;
+    const uint32_t ln = log2x16(n);
+    for (uint32_t s = (uint32_t)lane; s < 256u; s += 64) {
+        const uint32_t f = L.lfreq[s];
+        if (f) {
+            const uint32_t c = ln - log2x16(f);
+            cost += f * (c < 16u ? 16u : c);
+        }
+    }
+    for (int s = 1; s < 64; s <<= 1) cost += (uint32_t)__shfl_xor((int)cost, s);
+    const uint32_t lit16 = uni(cost) / n;       // >= 16
+    __syncthreads();
+    for (uint32_t k = (uint32_t)lane; k < 288u; k += 64) L.lfreq[k] = 0;
+    __syncthreads();
+
+    // ---- pass 1: matches, tokens, histograms ------------------------------------------------------
+    uint32_t ntok = 0, skip = 0;                // tokens so far; positions below `skip` are inside a match
+    uint32_t extra = 0;                         // this lane's tokens' extra bits
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t p = base + (uint32_t)lane;
+        const bool can = p + kMinMatch <= n;
+        const uint32_t v = load32u(T, p < n ? p : 0u);
+        const uint32_t h = (v * 2654435761u) >> (32 - kHashBits);
+        const uint32_t cand = can ? L.htab[h] : 0u;
+        __syncthreads();
+        if (can) atomicMax(&L.htab[h], p + 1u);
+        __syncthreads();
+        if (skip >= base + 64u) continue;       // (uniform) the whole step lies inside a match
+        uint32_t mlen = 0, mdist = 0;
+        if (cand && p >= skip) {
+            const uint32_t c = cand - 1u;       // < p: positions of earlier steps only
+            const uint32_t d = p - c;
+            if (d <= kMaxDist && load32u(T, c) == v) {
+                const uint32_t maxlen = n - p < kMaxMatch ? n - p : kMaxMatch;
+                uint32_t l = 4;
+                while (l < maxlen) {
+                    const uint32_t x = load32u(T, c + l) ^ load32u(T, p + l);
+                    if (x) {
+                        l += (uint32_t)(__ffs((int)x) - 1) >> 3;
+                        break;
+                    }
+                    l += 4;
+                }
+                l = l < maxlen ? l : maxlen;
+                // worth it if the length and distance codes (about 11 bits and the distance's extra
+                // bits) cost less than the bytes as literals
+                const uint32_t deb = d > 4u ? 30u - (uint32_t)__clz((int)(d - 1u)) : 0u;
+                if (l >= kMinMatch && l * lit16 >= 16u * (11u + deb)) {
+                    mlen = l;
+                    mdist = d;
+                }
+            }
+        }
+        const uint64_t found = __ballot(mlen != 0);
+        uint64_t starts = 0;                    // lanes whose match is taken
+        uint64_t cov = skip > base ? (1ull << (skip - base)) - 1ull : 0ull;   // lanes inside a match
+        uint32_t cur = skip > base ? skip - base : 0u;                        // < 64
+        while (cur < 64u) {
+            const uint64_t mm = found & ~((1ull << cur) - 1ull);
+            if (!mm) break;
+            const uint32_t l = (uint32_t)__ffsll((long long)mm) - 1u;
+            const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)l);
+            starts |= 1ull << l;
+            const uint32_t e = l + len;         // the first position after the match
+            const uint64_t upto = e >= 64u ? ~0ull : (1ull << e) - 1ull;
+            cov |= upto & ~((2ull << l) - 1ull);
+            cur = e;
+            skip = base + e;
+        }
+        const bool emit = p < n && !((cov >> lane) & 1ull);
+        const uint64_t em = __ballot(emit);
+        if (emit) {
+            const uint32_t at = ntok + (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
+            if ((starts >> lane) & 1ull) {
+                tok[at] = kTokMatch | ((mlen - 3u) << 16) | (mdist - 1u);
+                uint32_t s, eb, ev;
+                len_sym(mlen - 3u, s, eb, ev);
+                atomicAdd(&L.lfreq[s], 1u);
+                extra += eb;
+                dist_sym(mdist - 1u, s, eb, ev);
+                atomicAdd(&L.dfreq[s], 1u);
+                extra += eb;
+            } else {
+                tok[at] = v & 255u;
+                atomicAdd(&L.lfreq[v & 255u], 1u);
+            }
+        }
+        ntok += (uint32_t)__popcll(em);
+    }
+    for (int s = 1; s < 64; s <<= 1) extra += (uint32_t)__shfl_xor((int)extra, s);
+    extra = uni(extra);
+    if (lane == 0) L.lfreq[256] = 1;            // the end of the block
+    __threadfence_block();                      // the tokens, visible to the lanes that read them back
+    __syncthreads();
+
+    // ---- the codes ----------------------------------------------------------------------------------
+    Work &W = *reinterpret_cast<Work *>(L.htab);
+    bool ok = build_code(L.lfreq, 286, 15, L.llen, L.lcode, L.blc, W, lane);
+    ok = build_code(L.dfreq, 30, 15, L.dlen, L.dcode, L.blc, W, lane) && ok;
+    uint32_t data_bits = lane == 0 ? extra : 0u;   // the block's symbols (dummy symbols counted: an upper bound)
+    for (uint32_t s = (uint32_t)lane; s < 286u; s += 64) data_bits += L.lfreq[s] * L.llen[s];
+    if (lane < 30) data_bits += L.dfreq[lane] * L.dlen[lane];
+    for (int s = 1; s < 64; s <<= 1) data_bits += (uint32_t)__shfl_xor((int)data_bits, s);
+    data_bits = uni(data_bits);
+
+    // the code lengths in run-length form (symbols 16, 17, 18), by one lane
+    uint32_t hlit = 286, hdist = 30, nrle = 0;
+    if (lane == 0 && ok) {
+        while (hlit > 257u && L.llen[hlit - 1u] == 0) --hlit;
+        while (hdist > 1u && L.dlen[hdist - 1u] == 0) --hdist;
+        const uint32_t total = hlit + hdist;
+        uint32_t k = 0;
+        while (k < total) {
+            const uint32_t val = k < hlit ? L.llen[k] : L.dlen[k - hlit];
+            uint32_t run = 1;
+            while (k + run < total && (k + run < hlit ? L.llen[k + run] : L.dlen[k + run - hlit]) == val) ++run;
+            k += run;
+            if (val == 0) {
+                while (run >= 11u) {
+                    const uint32_t r = run < 138u ? run : 138u;
+                    L.rle[nrle++] = (uint16_t)(18u | ((r - 11u) << 8));
+                    ++L.cfreq[18];
+                    run -= r;
+                }
+                if (run >= 3u) {
+                    L.rle[nrle++] = (uint16_t)(17u | ((run - 3u) << 8));
+                    ++L.cfreq[17];
+                    run = 0;
+                }
+            } else {
+                L.rle[nrle++] = (uint16_t)val;
+                ++L.cfreq[val];
+                --run;
+                while (run >= 3u) {
+                    const uint32_t r = run < 6u ? run : 6u;
+                    L.rle[nrle++] = (uint16_t)(16u | ((r - 3u) << 8));
+                    ++L.cfreq[16];
+                    run -= r;
+                }
+            }
+            for (; run; --run) {
+                L.rle[nrle++] = (uint16_t)val;
+                ++L.cfreq[val];
+            }
+        }
+    }
+    hlit = uni(hlit);
+    hdist = uni(hdist);
+    nrle = uni(nrle);
+    ok = build_code(L.cfreq, 19, 7, L.clen, L.ccode, L.blc, W, lane) && ok;
+
+    // ---- the stream ---------------------------------------------------------------------------------
+    Out o;
+    o.a = (uint32_t)((uintptr_t)slot & 15u);
+    o.base = slot - o.a;
+    o.limit = o.a + FC2_DEFLATE_TILE_BOUND(tile);
+    o.stage0 = 0;
+    o.bit = 8ull * o.a;
+    o.over = false;
+    const uint32_t stored_bytes = n + (n > 65535u ? 10u : 5u);
+    if (lane == 0 && ok) {                      // the block's header
+        put(L, o, 1u | (2u << 1), 3);           // BFINAL, dynamic codes
+        uint32_t hclen = 19;
+        while (hclen > 4u && L.clen[kDClOrder[hclen - 1u]] == 0) --hclen;
+        put(L, o, hlit - 257u, 5);
+        put(L, o, hdist - 1u, 5);
+        put(L, o, hclen - 4u, 4);
+        for (uint32_t k = 0; k < hclen; ++k) put(L, o, L.clen[kDClOrder[k]], 3);
+        for (uint32_t k = 0; k < nrle; ++k) {
+            const uint32_t s = L.rle[k] & 255u, e = L.rle[k] >> 8;
+            put(L, o, L.ccode[s], L.clen[s]);
+            if (s >= 16u) put(L, o, e, s == 16u ? 2u : s == 17u ? 3u : 7u);
+        }
+    }
+    o.bit = ((uint64_t)uni((uint32_t)(o.bit >> 32)) << 32) | uni((uint32_t)o.bit);
+    __syncthreads();
+    const uint32_t dyn_bytes = (uint32_t)((o.bit - 8ull * o.a + data_bits + 7u) >> 3);
+    uint32_t len;
+    if (ok && dyn_bytes < stored_bytes) {
+        for (uint32_t b0 = 0; b0 < ntok; b0 += 64) {
+            const uint32_t k = b0 + (uint32_t)lane;
+            uint64_t bits = 0;
+            uint32_t nb = 0;
+            if (k < ntok) {
+                const uint32_t t = tok[k];
+                if (t & kTokMatch) {
+                    uint32_t s, eb, ev;
+                    len_sym((t >> 16) & 255u, s, eb, ev);
+                    bits = L.lcode[s];
+                    nb = L.llen[s];
+                    bits |= (uint64_t)ev << nb;
+                    nb += eb;
+                    dist_sym(t & 0x7FFFu, s, eb, ev);
+                    bits |= (uint64_t)L.dcode[s] << nb;
+                    nb += L.dlen[s];
+                    bits |= (uint64_t)ev << nb;
+                    nb += eb;                   // <= 15 + 5 + 15 + 13
+                } else {
+                    bits = L.lcode[t];
+                    nb = L.llen[t];
+                }
+            }
+            uint32_t incl = nb;                 // the bit counts' prefix sum over the lanes
+            for (int s = 1; s < 64; s <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)incl, (unsigned)s);
+                if (lane >= s) incl += up;
+            }
+            or_bits(L, o, o.bit + (incl - nb), bits, nb);
+            o.bit += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            flush_stage(L, o, lane);
+        }
+        if (lane == 0) or_bits(L, o, o.bit, L.lcode[256], L.llen[256]);
+        o.bit += L.llen[256];
+        __syncthreads();
+        const uint32_t end = (uint32_t)((o.bit + 7u) >> 3);
+        store_pieces(L, o, end, lane);
+        len = end - o.a;
+        if (o.over || len > FC2_DEFLATE_TILE_BOUND(tile)) len = kFailed;
+    } else {
+        // stored: one block, or 65535 bytes and the last one (LEN is 16 bits); byte k of the stream
+        for (uint32_t k = (uint32_t)lane; k < stored_bytes; k += 64) {
+            const uint32_t first = n > 65535u ? 65535u : n;
+            uint32_t b;
+            if (k < 5u) {
+                const uint32_t hd[5] = {n > 65535u ? 0u : 1u, first & 255u, first >> 8, ~first & 255u, (~first >> 8) & 255u};
+                b = hd[k];
+            } else if (k < 5u + first) {
+                b = (T[(k - 5u) >> 2] >> (8u * ((k - 5u) & 3u))) & 255u;
+            } else if (k < 10u + first) {        // (only with n = 65536: the second block holds one byte)
+                const uint32_t hd[5] = {1u, 1u, 0u, 0xFEu, 0xFFu};
+                b = hd[k - 5u - first];
+            } else {
+                b = (T[(k - 10u) >> 2] >> (8u * ((k - 10u) & 3u))) & 255u;
+            }
+            slot[k] = (uint8_t)b;
+        }
+        len = stored_bytes;
+    }
+    if (lane == 0) {
+        out_len[blk] = len;
+        crc[blk] = tile_crc;
+    }
+}
+
+size_t lds_bytes(uint32_t tile) { return offsetof(Lds, tile) + ((tile + 3u) & ~3u) + 16u; }
+
+}  // namespace
+
+extern "C" uint64_t fc2_deflate_scratch_bytes(uint64_t n_bytes, uint32_t tile) {
+    if (!tile || tile > kTileMax || !n_bytes) return 0;
+    const uint64_t tiles = (n_bytes + tile - 1) / tile;
+    return tiles * tile * sizeof(uint32_t);    // a token per input byte at most
+}
+
+extern "C" int fc2_deflate_launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride,
+                                  uint32_t *out_len, uint32_t *crc, void *scratch, void *stream) {
+    if (!tile || tile > kTileMax) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: tile must be 1..65536");
+    if (stride < FC2_DEFLATE_TILE_BOUND(tile))
+        return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: stride below FC2_DEFLATE_TILE_BOUND(tile)");
+    if (!n_bytes) return FC2_OK;
+    if (!src || !dst || !out_len || !crc || !scratch) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: null argument");
+    if (((uintptr_t)scratch & 3u) != 0) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: scratch must be 4-byte aligned");
+    const uint64_t tiles = (n_bytes + tile - 1) / tile;
+    if (tiles > 0x7FFFFFFFull) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: too many tiles for one launch");
+    // the kernel's LDS (over the 64 KiB a kernel gets unasked, for the larger tiles): once per device
+    static std::atomic<uint64_t> reserved{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: no current device");
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(reserved.load() & bit)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds_bytes(kTileMax)) != hipSuccess)
+            return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: cannot reserve the kernel's LDS");
+        reserved |= bit;
+    }
+    hipLaunchKernelGGL(deflate_kernel, dim3((uint32_t)tiles), dim3(64), lds_bytes(tile), (hipStream_t)stream, src, n_bytes,
+                       tile, dst, stride, out_len, crc, static_cast<uint32_t *>(scratch));
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_deflate_launch: ") + hipGetErrorString(e));
+}

@@ -72,7 +72,8 @@ class NativeCaller:
 
     def __init__(self, path: str, is_bam: bool, copts, genome_names, fasta_handle=None, write_reads=True,
                  write_multi=True, genome_dummy=False, known_circ: str = "", known_lin: str = "",
-                 bam_out: str = "", reads_gz=None, inflate_device=None, inflate_after: int = 0):
+                 bam_out: str = "", reads_gz=None, inflate_device=None, inflate_after: int = 0,
+                 gzip_device=None, gzip_tile: int = 0, gzip_timeout_s: float = 0.0):
         o = copts
         # the strings must outlive the handle's open call (fc2_caller_open copies them)
         self._keep = [o.name.encode(), known_circ.encode() if known_circ else None,
@@ -93,6 +94,9 @@ class NativeCaller:
         self.reads_gz = reads_gz     # (path, level, threads, piece): spliced_reads.fastq.gz written natively
         self.inflate_device = inflate_device   # a BGZF input's blocks inflated on this GPU (None: the CPU)
         self.inflate_after = inflate_after     # ... once this many bytes of the input were read
+        self.gzip_device = gzip_device         # spliced_reads.fastq.gz compressed on this GPU (None: the worker threads)
+        self.gzip_tile = gzip_tile             # ... in tiles of this many bytes (0: 32768), each a gzip member
+        self.gzip_timeout_s = gzip_timeout_s   # ... waiting at most this long for the device (0: 60 s)
         self.opened = False
         self.format = None           # "sam" | "bam", detected from the bytes (open)
         self.loop_profile = {}       # seconds per stage of the last run (two-thread loop)
@@ -114,6 +118,9 @@ class NativeCaller:
         if self.reads_gz:
             path, level, threads, piece = self.reads_gz
             N.check(L.fc2_caller_set_reads_gz(self.h, path.encode(), int(level), int(threads), int(piece)))
+            if self.gzip_device is not None:
+                N.check(L.fc2_caller_set_reads_gz_device_tuning(self.h, int(self.gzip_tile), float(self.gzip_timeout_s)))
+                N.check(L.fc2_caller_set_reads_gz_device(self.h, int(self.gzip_device)))
         n_ref = L.fc2_ingest_n_refs(ing)
         self.refs = [L.fc2_ingest_ref_name(ing, t).decode("latin-1") for t in range(n_ref)]
         index = {nm: k for k, nm in enumerate(self.genome_names)}
@@ -137,6 +144,13 @@ class NativeCaller:
         """(BGZF blocks inflated on the GPU, on the CPU) since the GPU inflate was set (0, 0 without)."""
         g, c = ctypes.c_uint64(), ctypes.c_uint64()
         N.check(N.lib().fc2_caller_inflate_counts(self.h, ctypes.byref(g), ctypes.byref(c)))
+        return int(g.value), int(c.value)
+
+    def reads_gz_counts(self):
+        """(pieces of spliced_reads.fastq.gz the GPU compressed, pieces its device mode left to the CPU);
+        (0, 0) without gzip_device."""
+        g, c = ctypes.c_uint64(), ctypes.c_uint64()
+        N.check(N.lib().fc2_caller_reads_gz_counts(self.h, ctypes.byref(g), ctypes.byref(c)))
         return int(g.value), int(c.value)
 
     def stats(self):

@@ -116,6 +116,37 @@ int fc2_caller_set_reads_gz(fc2_caller *h, const char *path, int level, int thre
 /* Compress and write what is left and close the file (also done, errors ignored, by
  * fc2_caller_close); FC2_E_IO if a write failed. */
 int fc2_caller_close_reads(fc2_caller *h);
+/* spliced_reads.fastq.gz compressed on GPU `device` instead of the worker threads (fc2_deflate.hip): call after
+ * fc2_caller_set_reads_gz and before the first fc2_caller_submit.  The level is then ignored; every tile of a
+ * piece (32768 bytes; FC2_GPU_GZIP_TILE: 1..65536) is its own gzip member.  If the device fails, the CPU
+ * compresses from that piece on.  A device that does not answer within FC2_GPU_GZIP_TIMEOUT_S (60) seconds
+ * makes fc2_caller_close_reads fail with FC2_E_IO.  The device mode holds four pieces in flight: 64 MiB of
+ * pinned host memory and 192 MiB of device memory at the default piece of 4 MiB. */
+int fc2_caller_set_reads_gz_device(fc2_caller *h, int device);
+/* This handle's tile (0: 32768) and longest wait for the device in seconds (0: 60), for the device mode
+ * set afterwards with fc2_caller_set_reads_gz_device.  The command line passes FC2_GPU_GZIP_TILE and
+ * FC2_GPU_GZIP_TIMEOUT_S here; the library itself reads no environment variable for them. */
+int fc2_caller_set_reads_gz_device_tuning(fc2_caller *h, uint32_t tile, double timeout_s);
+/* pieces the device compressed, and pieces of the device mode the CPU compressed, so far (0, 0 without it) */
+int fc2_caller_reads_gz_counts(const fc2_caller *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces);
+
+/* ---- the DEFLATE compressor on the GPU (csrc/fc2_deflate.hip) ---- */
+/* the most bytes a tile's stream takes: stored blocks (5 bytes each, two for a tile of 65536) when the
+ * Huffman form would not be smaller */
+#define FC2_DEFLATE_TILE_BOUND(tile) ((uint32_t)(tile) + 16u)
+/* n_bytes of src (device) cut into tiles of `tile` bytes; tile i's raw DEFLATE stream goes to
+ * dst + i * stride (stride >= FC2_DEFLATE_TILE_BOUND(tile)), its length to out_len[i], the gzip CRC-32 of
+ * its input to crc[i]; scratch: fc2_deflate_scratch_bytes(n_bytes, tile) bytes of device memory.  Nothing
+ * outside [dst + i * stride, + out_len[i]) is written.  out_len[i] = 0xFFFFFFFF: the kernel gave the tile up
+ * (not expected; the caller compresses it). */
+int fc2_deflate_launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride,
+                       uint32_t *out_len, uint32_t *crc, void *scratch, void *stream);
+uint64_t fc2_deflate_scratch_bytes(uint64_t n_bytes, uint32_t tile);
+/* one buffer through the host path of spliced_reads.fastq.gz's device mode, for tests and other hosts: gzip
+ * members (one per tile) of in[0, n) into out (cap bytes); FC2_E_RANGE if they do not fit. */
+int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, void *out, uint64_t cap, uint64_t *out_n);
+uint64_t fc2_gpu_gzip_bound(uint64_t n, uint32_t tile);
+
 /* The BED rows (no header) of 0 = circ_splice_sites.bed, 1 = lin_splice_sites.bed
  * (call once, at the end).  Once the input was read to its end and every chunk submitted, the first
  * call releases the read side -- the input (so finish -B output with fc2_ingest_close_bam_out
