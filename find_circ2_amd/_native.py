@@ -155,6 +155,7 @@ EXPORTED = [
     "fc2_ingest_next", "fc2_ingest_counts_get", "fc2_ingest_set_bam_out", "fc2_ingest_close_bam_out",
     "fc2_ingest_format", "fc2_sam_to_bam", "fc2_bgzf_inflate_launch",
     "fc2_ingest_set_gpu_inflate", "fc2_ingest_set_gpu_inflate_from", "fc2_ingest_inflate_counts",
+    "fc2_bam_walk_launch", "fc2_bam_walk_host", "fc2_ingest_set_gpu_walk", "fc2_ingest_walk_counts",
     # include/fc2_caller.h
     "fc2_caller_open", "fc2_caller_set_genome", "fc2_caller_inflate_counts", "fc2_caller_ingest", "fc2_caller_close", "fc2_caller_next",
     "fc2_caller_submit", "fc2_caller_submit_compact", "fc2_caller_submit_long", "fc2_caller_queued", "fc2_caller_take", "fc2_caller_rows", "fc2_caller_write_rows", "fc2_caller_counter", "fc2_caller_stats",
@@ -164,6 +165,11 @@ EXPORTED = [
     "fc2_ctx_create", "fc2_ctx_create_sibling", "fc2_ctx_destroy", "fc2_ctx_genome_load", "fc2_ctx_genome_view", "fc2_ctx_scan_async",
     "fc2_ctx_sync", "fc2_ctx_scan_long", "fc2_ctx_stream", "fc2_ctx_last_error",
 ]
+
+
+# include/fc2_ingest.h: entries of a block's row of record starts, and "the walk does not leave the block"
+BAM_WALK_CAP = 1824
+BAM_WALK_NO_EXIT = 0xFFFFFFFF
 
 
 class IngestParams(ctypes.Structure):
@@ -308,6 +314,10 @@ def lib() -> ctypes.CDLL:
         "fc2_ingest_set_gpu_inflate": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
         "fc2_ingest_set_gpu_inflate_from": (ctypes.c_int, [vp, ctypes.c_int, u64]),
         "fc2_ingest_inflate_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
+        "fc2_bam_walk_launch": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, u32, vp]),
+        "fc2_bam_walk_host": (ctypes.c_int, [vp, u32, vp, P(u32), P(u32)]),
+        "fc2_ingest_set_gpu_walk": (ctypes.c_int, [vp, ctypes.c_int]),
+        "fc2_ingest_walk_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "fc2_caller_inflate_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "fc2_ctx_create": (ctypes.c_int, [ctypes.c_int, P(vp)]),
         "fc2_ctx_create_sibling": (ctypes.c_int, [vp, P(vp)]),

@@ -283,6 +283,12 @@ def _inflate_device(options):
     return device_index(options.device), (0 if env in ("1", "2") else GPU_INFLATE_AFTER)
 
 
+def _gpu_walk():
+    """Whether the GPU that inflates the BAM input also lists its blocks' record starts (DESIGN.md §5 "The
+    BAM input inflated on the GPU"): yes, unless FC2_GPU_WALK=0, which leaves them to host threads."""
+    return os.environ.get("FC2_GPU_WALK") != "0"
+
+
 def _gzip_device(options):
     """spliced_reads.fastq.gz compressed on the GPU: only with FC2_GPU_GZIP=1, on the first of
     the run's devices, in tiles of FC2_GPU_GZIP_TILE bytes (32768), waiting at most
@@ -316,7 +322,7 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                       write_multi=out.get("multi") is not None, genome_dummy=dummy,
                       known_circ=options.known_circ, known_lin=options.known_lin, bam_out=bam_path,
                       reads_gz=reads_gz,
-                      **(dict(zip(("inflate_device", "inflate_after"), _inflate_device(options)))
+                      **(dict(zip(("inflate_device", "inflate_after"), _inflate_device(options)), gpu_walk=_gpu_walk())
                          if genome_eval is not None else {}),
                       **(_gzip_device(options) if genome_eval is not None and reads_gz else {}))
     try:

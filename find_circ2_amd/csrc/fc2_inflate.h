@@ -24,10 +24,15 @@ uint32_t gpu_max_blocks(const Gpu *g);
 // copied, then uploaded, inflated -- CRC-32 and ISIZE checked on the device -- and downloaded while
 // the next chunk is read), then gpu_finish, which waits: false (err set) if the device failed.
 // Afterwards gpu_status(g, i) == 0 for each block whose bytes are in dest; the others are the CPU's.
-void gpu_begin(Gpu *g, char *dest);
+// With walk, the device also lists every inflated block's BAM record starts (bam_walk_kernel: what
+// fc2_ingest.cpp's walk_block finds), downloaded with the bytes: after gpu_finish, gpu_walk(g, i, ...)
+// for a block with status 0 is its row of `count` ascending offsets into the block and the offset the
+// walk leaves the block at (FC2_BAM_WALK_NO_EXIT: nowhere).
+void gpu_begin(Gpu *g, char *dest, bool walk);
 bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, size_t i0, size_t i1);
 bool gpu_finish(Gpu *g, std::string &err);
 uint32_t gpu_status(const Gpu *g, size_t i);
+const uint16_t *gpu_walk(const Gpu *g, size_t i, uint32_t &count, uint32_t &exit);
 
 // a pinned buffer of >= n bytes from the pool (nullptr: no pool, too large, or none left)
 void *pinned_take(size_t n);

@@ -448,7 +448,103 @@ __global__ __launch_bounds__(256) void compact_kernel(const uint8_t *__restrict_
     for (uint32_t i = 0; i < k; ++i) d[i] = (uint8_t)(w[i >> 2] >> (8u * (i & 3u)));
 }
 
+// ---- the BAM record starts of the inflated blocks (fc2_ingest.cpp walk_block, on the device) ------
+// One wavefront per block, reading the block where the inflate kernel left it: its slot, in L2 or
+// HBM, no LDS (the chain of block sizes is ~250 dependent loads a block, and a chunk's 256 wavefronts
+// wait for them side by side; staging 64 KiB a block in LDS would leave room for two of these
+// workgroups a CU and none for the inflate kernel's eight).  Every read is below min(isize, 64 KiB)
+// of the block's own slot and every write inside its own output row, whatever the bytes say.
+
+constexpr uint32_t kWalkCap = FC2_BAM_WALK_CAP;
+static_assert((kOutMax - 4) / 36 + 1 <= kWalkCap, "a block's record starts fit a row");
+
+// the little-endian 32-bit field at byte o of the slot (w: its words), from aligned words, so a
+// record start at any byte residue reads the same way; o + 4 <= 64 KiB
+__device__ __forceinline__ uint32_t walk_u32(const uint32_t *__restrict__ w, uint32_t o) {
+    const uint32_t i = o >> 2, s = (o & 3u) * 8u;
+    const uint32_t lo = w[i];
+    if (!s) return lo;
+    return (lo >> s) | (w[i + 1] << (32u - s));
+}
+
+// bam_plausible (fc2_ingest.cpp) at byte o of a block of n bytes
+__device__ bool walk_plausible(const uint32_t *__restrict__ w, uint32_t o, uint32_t n) {
+    if (o > n || n - o < 36u) return false;
+    const uint32_t avail = n - o;
+    const int32_t bs = (int32_t)walk_u32(w, o);
+    if (bs < 32 || bs >= (1 << 28)) return false;
+    const int32_t ref = (int32_t)walk_u32(w, o + 4), pos = (int32_t)walk_u32(w, o + 8);
+    const uint32_t lname = walk_u32(w, o + 12) & 0xFFu, ncig = walk_u32(w, o + 16) & 0xFFFFu;
+    const int32_t lseq = (int32_t)walk_u32(w, o + 20), nref = (int32_t)walk_u32(w, o + 24),
+                  npos = (int32_t)walk_u32(w, o + 28);
+    if (ref < -1 || pos < -1 || lname < 1 || lseq < 0 || nref < -1 || npos < -1) return false;
+    if (32ull + lname + 4ull * ncig + ((uint64_t)lseq + 1) / 2 + (uint64_t)lseq > (uint64_t)bs) return false;
+    if (36u + lname > avail) return true;
+    const uint8_t *p = reinterpret_cast<const uint8_t *>(w) + o + 36u;     // lname bytes, all below n
+    if (p[lname - 1] != 0) return false;
+    for (uint32_t k = 0; k + 1 < lname; ++k)
+        if (p[k] < 0x21 || p[k] > 0x7e) return false;
+    return true;
+}
+
+__global__ __launch_bounds__(64) void bam_walk_kernel(const uint8_t *__restrict__ slots, const uint32_t *__restrict__ isize,
+                                                      const uint32_t *__restrict__ status, uint16_t *__restrict__ starts,
+                                                      uint32_t *__restrict__ count, uint32_t *__restrict__ exit_at) {
+    const uint32_t blk = blockIdx.x, lane = threadIdx.x;
+    if (status && status[blk] != INF_OK) {      // not inflated: the host walks it once the CPU has
+        if (lane == 0) count[blk] = 0, exit_at[blk] = FC2_BAM_WALK_NO_EXIT;
+        return;
+    }
+    const uint32_t n = min(isize[blk], kOutMax);
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(slots + (uint64_t)blk * kOutMax);
+    uint16_t *row = starts + (uint64_t)blk * kWalkCap;
+    // the first plausible record followed by a plausible one (or by the block's end): 64 offsets a
+    // step, the lowest lane that holds wins; at most n / 64 steps
+    uint32_t o = FC2_BAM_WALK_NO_EXIT;
+    for (uint32_t b = 0; b + 36u <= n; b += 64u) {
+        const uint32_t c = b + lane;
+        bool ok = walk_plausible(w, c, n);
+        if (ok) {
+            const uint32_t nx = c + 4u + walk_u32(w, c);                    // (block_size < 2^28)
+            ok = nx + 36u > n || walk_plausible(w, nx, n);
+        }
+        const unsigned long long m = __ballot(ok);
+        if (m) {
+            o = b + (uint32_t)__ffsll(m) - 1u;
+            break;
+        }
+    }
+    o = uni(o);
+    uint32_t cnt = 0, ex = FC2_BAM_WALK_NO_EXIT;
+    if (o != FC2_BAM_WALK_NO_EXIT) {
+        // block_size to block_size: every step advances at least 36 bytes, so at most kWalkCap steps
+        // (o stays below 64 KiB + 4 + 2^31: no overflow)
+        bool cut = false;
+        while (cnt < kWalkCap && o + 4u <= n) {
+            const int32_t bs = (int32_t)uni(walk_u32(w, o));
+            if (bs < 32) { cut = true; break; }
+            if (lane == 0) row[cnt] = (uint16_t)o;
+            ++cnt;
+            o += 4u + (uint32_t)bs;
+        }
+        if (!cut) ex = o;
+    }
+    if (lane == 0) count[blk] = cnt, exit_at[blk] = ex;
+}
+
 }  // namespace
+
+// C ABI (include/fc2_ingest.h): the record starts of n_blocks inflated blocks
+extern "C" int fc2_bam_walk_launch(const uint8_t *slots, const uint32_t *isize, const uint32_t *status, uint16_t *starts,
+                                   uint32_t *count, uint32_t *exit, uint32_t n_blocks, void *stream) {
+    if (!n_blocks) return FC2_OK;
+    if (!slots || !isize || !starts || !count || !exit) return fc2::fail(FC2_E_PARAM, "fc2_bam_walk_launch: null argument");
+    if ((uintptr_t)slots & 3u) return fc2::fail(FC2_E_PARAM, "fc2_bam_walk_launch: slots must be 4-byte aligned");
+    hipLaunchKernelGGL(bam_walk_kernel, dim3(n_blocks), dim3(64), 0, (hipStream_t)stream, slots, isize, status, starts,
+                       count, exit);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_bam_walk_launch: ") + hipGetErrorString(e));
+}
 
 // C ABI (include/fc2_ingest.h): n blocks; src must be readable 8 bytes past every payload
 extern "C" int fc2_bgzf_inflate_launch(const uint8_t *src, const uint32_t *off, const uint32_t *len,
@@ -568,6 +664,10 @@ struct Gpu {
     hipEvent_t done[kStreams] = {};            // blocking-sync: the reader thread sleeps, not spins
     uint8_t *h_src = nullptr, *d_src = nullptr, *d_slots = nullptr, *d_out = nullptr;
     uint32_t *h_meta = nullptr, *d_meta = nullptr;      // off | len | isize | crc | ooff | status
+    // the blocks' record lists (bam_walk_kernel): count | exit, and a row of starts per block
+    uint32_t *h_walk = nullptr, *d_walk = nullptr;
+    uint16_t *h_starts = nullptr, *d_starts = nullptr;
+    bool walk = false;                         // this batch's blocks are listed on the device
     bool pooled = false;
     // the batch under way (gpu_begin .. gpu_finish)
     char *dest = nullptr;
@@ -591,6 +691,7 @@ Gpu *gpu_open(int device, uint32_t max_blocks, size_t pool_cap, std::string &err
     g->max_blocks = max_blocks;
     g->src_cap = (size_t)max_blocks * kOutMax + 64;      // a BGZF block is at most 64 KiB
     const size_t out = (size_t)max_blocks * kOutMax, meta = (size_t)max_blocks * 6 * sizeof(uint32_t);
+    const size_t walk = (size_t)max_blocks * 2 * sizeof(uint32_t), rows = (size_t)max_blocks * kWalkCap * sizeof(uint16_t);
     bool ok = hip_ok(g, hipSetDevice(device), "hipSetDevice");
     for (int k = 0; k < kStreams && ok; ++k)
         ok = hip_ok(g, hipStreamCreateWithFlags(&g->stream[k], hipStreamNonBlocking), "stream") &&
@@ -600,7 +701,11 @@ Gpu *gpu_open(int device, uint32_t max_blocks, size_t pool_cap, std::string &err
          hip_ok(g, hipMalloc((void **)&g->d_src, g->src_cap), "device input") &&
          hip_ok(g, hipMalloc((void **)&g->d_slots, out), "device slots") &&
          hip_ok(g, hipMalloc((void **)&g->d_out, out), "device output") &&
-         hip_ok(g, hipMalloc((void **)&g->d_meta, meta), "device table");
+         hip_ok(g, hipMalloc((void **)&g->d_meta, meta), "device table") &&
+         hip_ok(g, hipHostMalloc((void **)&g->h_walk, walk, hipHostMallocDefault), "pinned record counts") &&
+         hip_ok(g, hipHostMalloc((void **)&g->h_starts, rows, hipHostMallocDefault), "pinned record lists") &&
+         hip_ok(g, hipMalloc((void **)&g->d_walk, walk), "device record counts") &&
+         hip_ok(g, hipMalloc((void **)&g->d_starts, rows), "device record lists");
     if (!ok) {
         err = g->err;
         gpu_close(g);
@@ -622,6 +727,10 @@ void gpu_close(Gpu *g) {
     if (hipSetDevice(g->device) == hipSuccess) {
         for (int k = 0; k < kStreams; ++k)
             if (g->stream[k]) (void)hipStreamSynchronize(g->stream[k]);
+        if (g->d_starts) (void)hipFree(g->d_starts);
+        if (g->d_walk) (void)hipFree(g->d_walk);
+        if (g->h_starts) (void)hipHostFree(g->h_starts);
+        if (g->h_walk) (void)hipHostFree(g->h_walk);
         if (g->d_meta) (void)hipFree(g->d_meta);
         if (g->d_out) (void)hipFree(g->d_out);
         if (g->d_slots) (void)hipFree(g->d_slots);
@@ -639,8 +748,9 @@ void gpu_close(Gpu *g) {
 
 uint32_t gpu_max_blocks(const Gpu *g) { return g->max_blocks; }
 
-void gpu_begin(Gpu *g, char *dest) {
+void gpu_begin(Gpu *g, char *dest, bool walk) {
     g->dest = dest;
+    g->walk = walk;
     g->n = 0;
     g->out = 0;
     g->chunks = 0;
@@ -699,8 +809,21 @@ bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, 
     hipLaunchKernelGGL(compact_kernel, dim3(kOutMax / 16 / 256, c), dim3(256), 0, s, g->d_slots + (size_t)i0 * kOutMax,
                        d_isz + i0, d_ooff + i0, d_st + i0, g->d_out);
     const uint64_t o0 = ooff[i0];
-    return hip_ok(g, hipGetLastError(), "compact") &&
-           hip_ok(g, hipMemcpyAsync(g->dest + o0, g->d_out + o0, g->out - o0, hipMemcpyDeviceToHost, s), "download") &&
+    if (!hip_ok(g, hipGetLastError(), "compact")) return false;
+    if (g->walk) {                             // the blocks' record lists, from the slots the compaction leaves as they are
+        if (fc2_bam_walk_launch(g->d_slots + (size_t)i0 * kOutMax, d_isz + i0, d_st + i0, g->d_starts + (size_t)i0 * kWalkCap,
+                                g->d_walk + i0, g->d_walk + M + i0, c, s) != FC2_OK) {
+            if (g->ok) g->err = "GPU inflate: record list launch failed";
+            g->ok = false;
+            return false;
+        }
+        ok = hip_ok(g, hipMemcpyAsync(g->h_starts + (size_t)i0 * kWalkCap, g->d_starts + (size_t)i0 * kWalkCap,
+                                      (size_t)c * kWalkCap * sizeof(uint16_t), hipMemcpyDeviceToHost, s), "download") &&
+             hip_ok(g, hipMemcpyAsync(g->h_walk + i0, g->d_walk + i0, c * w, hipMemcpyDeviceToHost, s), "download") &&
+             hip_ok(g, hipMemcpyAsync(g->h_walk + M + i0, g->d_walk + M + i0, c * w, hipMemcpyDeviceToHost, s), "download");
+        if (!ok) return false;
+    }
+    return hip_ok(g, hipMemcpyAsync(g->dest + o0, g->d_out + o0, g->out - o0, hipMemcpyDeviceToHost, s), "download") &&
            hip_ok(g, hipMemcpyAsync(st + i0, d_st + i0, c * w, hipMemcpyDeviceToHost, s), "download");
 }
 
@@ -712,6 +835,12 @@ bool gpu_finish(Gpu *g, std::string &err) {
 }
 
 uint32_t gpu_status(const Gpu *g, size_t i) { return g->h_meta[5 * (size_t)g->max_blocks + i]; }
+
+const uint16_t *gpu_walk(const Gpu *g, size_t i, uint32_t &count, uint32_t &exit) {
+    count = std::min<uint32_t>(g->h_walk[i], kWalkCap);
+    exit = g->h_walk[(size_t)g->max_blocks + i];
+    return g->h_starts + i * kWalkCap;
+}
 
 }  // namespace inf
 }  // namespace fc2

@@ -284,6 +284,11 @@ struct GpuInflate {
     bool failed = false;                       // the device could not be had or failed: CPU from then on
     std::string err;
     std::atomic<uint64_t> gpu_blocks{0}, cpu_blocks{0};
+    // fc2_ingest_set_gpu_walk: the blocks the device inflated take their record lists (RecLists) from it
+    // too (fc2_inflate.hip bam_walk_kernel), read by the batch reader at the start of each batch; the
+    // blocks listed there, and those left to the host threads (of the batches the GPU took)
+    std::atomic<bool> walk{true};
+    std::atomic<uint64_t> walk_dev_blocks{0}, walk_cpu_blocks{0};
     // FC2_CALLER_TIMING: the batch reader's time reading, submitting chunks, waiting for the device,
     // inflating refused blocks; batches whose buffer was pinned (downloaded into directly)
     int64_t read_ns = 0, add_ns = 0, wait_ns = 0, cpu_ns = 0;
@@ -309,9 +314,11 @@ struct GpuInflate {
     ~GpuInflate() {
         if (getenv("FC2_CALLER_TIMING") && batches)
             fprintf(stderr, "gpu inflate: %d batches (%d pinned), %llu blocks on the GPU, %llu on the CPU; reader s: "
-                    "read %.3f submit %.3f wait %.3f cpu %.3f\n", batches, pinned, (unsigned long long)gpu_blocks.load(),
-                    (unsigned long long)cpu_blocks.load(), (read_ns - add_ns) * 1e-9, add_ns * 1e-9, wait_ns * 1e-9,
-                    cpu_ns * 1e-9);
+                    "read %.3f submit %.3f wait %.3f cpu %.3f\n"
+                    "gpu walk: record lists of %llu blocks from the device, %llu walked on the host\n", batches, pinned,
+                    (unsigned long long)gpu_blocks.load(), (unsigned long long)cpu_blocks.load(), (read_ns - add_ns) * 1e-9,
+                    add_ns * 1e-9, wait_ns * 1e-9, cpu_ns * 1e-9, (unsigned long long)walk_dev_blocks.load(),
+                    (unsigned long long)walk_cpu_blocks.load());
         if (opening.valid()) g = opening.get().first;
         fc2::inf::gpu_close(g);
     }
@@ -342,6 +349,7 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
         if (!gi->g) gi->failed = true, gi->err = r.second;
     }
     gpu = gpu && gi->g;
+    const bool dev_lists = gpu && gi->walk.load();
     size_t submitted = 0;
     auto submit = [&](bool last) {             // blocks read so far, in chunks of kGpuChunk
         if (!gpu) return;
@@ -355,7 +363,7 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
     const int64_t t0 = now_ns();
     if (gpu) {
         B.out.resize(kHead + (size_t)max_blocks * 65536);
-        fc2::inf::gpu_begin(gi->g, B.out.data() + kHead);
+        fc2::inf::gpu_begin(gi->g, B.out.data() + kHead, dev_lists);
         gi->batches += 1;
         gi->pinned += fc2::inf::pinned_owns(B.out.data());
     }
@@ -429,6 +437,20 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
         R->starts.resize(nb);
         R->exit.assign(nb, kNoExit);
     }
+    // ... or, for the blocks the device inflated, by the device: its rows, moved to batch offsets
+    const bool listed = R && on_gpu && dev_lists;
+    if (listed) {
+        fc2::cpu::Scope acct(fc2::cpu::INFLATE);
+        for (size_t i = 0; i < nb; ++i) {
+            if (on_cpu[i]) continue;
+            uint32_t cnt, ex;
+            const uint16_t *row = fc2::inf::gpu_walk(gi->g, i, cnt, ex);
+            std::vector<uint32_t> &st = R->starts[i];
+            st.resize(cnt);
+            for (uint32_t k = 0; k < cnt; ++k) st[k] = (uint32_t)ooff[i] + row[k];
+            R->exit[i] = ex == FC2_BAM_WALK_NO_EXIT ? kNoExit : ooff[i] + (uint64_t)ex;
+        }
+    }
     std::atomic<size_t> next{0};
     std::atomic<bool> bad{false};
     auto work = [&]() {
@@ -436,6 +458,7 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
         fc2::dfl::Inflater inf;                 // libdeflate (zlib without it): fc2_deflate.h
         if (!inf.ok()) { bad = true; return; }
         for (size_t i; (i = next.fetch_add(1)) < nb && !bad;) {
+            if (listed && !on_cpu[i]) continue;
             char *dst = B.out.data() + kHead + ooff[i];
             const size_t n = ooff[i + 1] - ooff[i];
             if (on_cpu[i]) {
@@ -451,7 +474,9 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
             if (R) walk_block(B.out.data() + kHead, ooff[i], ooff[i + 1], R->starts[i], R->exit[i]);
         }
     };
-    const int nt = (int)std::min<size_t>((size_t)n_threads, R ? nb : n_cpu);
+    // (the threads: as many as there are blocks the CPU must still inflate or walk -- none for a batch
+    // the device inflated and listed whole)
+    const int nt = (int)std::min<size_t>((size_t)n_threads, R && !listed ? nb : n_cpu);
     std::vector<std::thread> pool;
     for (int t = 1; t < nt; ++t) pool.emplace_back(work);
     if (nt > 0) work();
@@ -460,6 +485,8 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
     if (gpu) {                                 // (the batches the GPU took: its blocks, and those it refused)
         gi->gpu_blocks += nb - n_cpu;
         gi->cpu_blocks += n_cpu;
+        gi->walk_dev_blocks += listed ? nb - n_cpu : 0;
+        gi->walk_cpu_blocks += !R ? 0 : listed ? n_cpu : nb;
         gi->cpu_ns += now_ns() - t2;
     }
     return B;
@@ -494,6 +521,7 @@ struct fc2_ingest {
     int bgzf_blocks = 256;       // BGZF blocks per inflated batch (FC2_BGZF_BATCH: small in the tests)
     std::future<BgzfBatch> bgzf_next;
     std::shared_ptr<GpuInflate> gpu_inflate;     // fc2_ingest_set_gpu_inflate (null: the CPU inflates)
+    bool gpu_walk = true;                        // fc2_ingest_set_gpu_walk, for a GPU inflate set later
     std::atomic<int64_t> inflate_wait_ns{0};     // the reader's wait for inflated BGZF batches (timing)
     std::string z_err;
     // header
@@ -1928,6 +1956,7 @@ extern "C" int fc2_ingest_set_gpu_inflate_from(fc2_ingest *h, int device, uint64
     }
     auto gi = std::make_shared<GpuInflate>();
     gi->device = device;
+    gi->walk = h->gpu_walk;
     // batches of 1024 blocks (64 MiB inflated, four chunks of 256; fc2_inflate.hip) once the GPU
     // inflates; FC2_BGZF_BATCH still rules
     gi->max_blocks = getenv("FC2_BGZF_BATCH") ? (uint32_t)h->bgzf_blocks : 1024u;
@@ -1960,6 +1989,7 @@ extern "C" int fc2_ingest_set_gpu_inflate(fc2_ingest *h, int device, int wait) {
     }
     auto gi = std::make_shared<GpuInflate>();
     gi->device = device;
+    gi->walk = h->gpu_walk;
     gi->max_blocks = getenv("FC2_BGZF_BATCH") ? (uint32_t)h->bgzf_blocks : 1024u;
     gi->launch(true);
     auto r = gi->opening.get();
@@ -1974,6 +2004,35 @@ extern "C" int fc2_ingest_inflate_counts(const fc2_ingest *h, uint64_t *gpu_bloc
     const GpuInflate *gi = h->gpu_inflate.get();
     if (gpu_blocks) *gpu_blocks = gi ? gi->gpu_blocks.load() : 0;
     if (cpu_blocks) *cpu_blocks = gi ? gi->cpu_blocks.load() : 0;
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_set_gpu_walk(fc2_ingest *h, int on) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_walk: null argument");
+    h->gpu_walk = on != 0;
+    if (GpuInflate *gi = h->gpu_inflate.get()) gi->walk = on != 0;      // (the batch reader may be running: atomic)
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_walk_counts(const fc2_ingest *h, uint64_t *device_blocks, uint64_t *cpu_blocks) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_walk_counts: null argument");
+    const GpuInflate *gi = h->gpu_inflate.get();
+    if (device_blocks) *device_blocks = gi ? gi->walk_dev_blocks.load() : 0;
+    if (cpu_blocks) *cpu_blocks = gi ? gi->walk_cpu_blocks.load() : 0;
+    return FC2_OK;
+}
+
+// walk_block on one block, in the form of the device's rows (fc2_bam_walk_launch)
+extern "C" int fc2_bam_walk_host(const uint8_t *block, uint32_t n, uint16_t *starts, uint32_t *count, uint32_t *exit) {
+    if ((!block && n) || !starts || !count || !exit) return fc2::fail(FC2_E_PARAM, "fc2_bam_walk_host: null argument");
+    if (n > 65536) return fc2::fail(FC2_E_RANGE, "fc2_bam_walk_host: a block holds at most 65536 bytes");
+    std::vector<uint32_t> st;
+    uint64_t ex;
+    walk_block((const char *)block, 0, n, st, ex);
+    const size_t c = std::min<size_t>(st.size(), FC2_BAM_WALK_CAP);
+    for (size_t k = 0; k < c; ++k) starts[k] = (uint16_t)st[k];
+    *count = (uint32_t)c;
+    *exit = ex == kNoExit ? FC2_BAM_WALK_NO_EXIT : (uint32_t)ex;
     return FC2_OK;
 }
 

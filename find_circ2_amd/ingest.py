@@ -69,6 +69,18 @@ class NativeIngest:
         N.check(N.lib().fc2_ingest_inflate_counts(self.h, ctypes.byref(g), ctypes.byref(c)))
         return int(g.value), int(c.value)
 
+    def set_gpu_walk(self, on: bool):
+        """Whether the blocks the GPU inflates take their record lists from the device too (the default)
+        or from host threads (fc2_ingest_set_gpu_walk); holds from the next batch on."""
+        N.check(N.lib().fc2_ingest_set_gpu_walk(self.h, int(bool(on))))
+
+    def walk_counts(self) -> Tuple[int, int]:
+        """(blocks whose record lists came from the device, blocks walked on the host) of the batches
+        the GPU inflated."""
+        d, c = ctypes.c_uint64(), ctypes.c_uint64()
+        N.check(N.lib().fc2_ingest_walk_counts(self.h, ctypes.byref(d), ctypes.byref(c)))
+        return int(d.value), int(c.value)
+
     def close_bam_out(self):
         N.check(N.lib().fc2_ingest_close_bam_out(self.h))
 

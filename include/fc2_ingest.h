@@ -108,6 +108,33 @@ int fc2_ingest_inflate_counts(const fc2_ingest *h, uint64_t *gpu_blocks, uint64_
  * CRC-32); status[i] = 0, or why the block was refused (the host then inflates it on the CPU). */
 int fc2_bgzf_inflate_launch(const uint8_t *src, const uint32_t *off, const uint32_t *len, const uint32_t *isize,
                             const uint32_t *crc, uint8_t *dst, uint32_t *status, uint32_t n, void *stream);
+
+/* The BAM record starts of inflated BGZF blocks, listed on the GPU (fc2_inflate.hip bam_walk_kernel) for the
+ * ingest's splitter: per block, the record starts a walk visits when it begins at the block's first
+ * plausible record -- one followed by another plausible record or by the block's end -- and goes from
+ * block_size to block_size, and where that walk leaves the block.  A row of `starts` holds
+ * FC2_BAM_WALK_CAP entries: a step advances at least 4 + 32 bytes and the last start is at most
+ * 65536 - 4, so a block has at most (65536 - 4) / 36 + 1 = 1821 of them (1824: rows of whole 16 bytes). */
+#define FC2_BAM_WALK_CAP 1824
+#define FC2_BAM_WALK_NO_EXIT 0xFFFFFFFFu
+/* n_blocks blocks, block i = isize[i] <= 65536 bytes at slots + i * 65536 (device memory, 4-byte aligned:
+ * the slots fc2_bgzf_inflate_launch fills), on `stream`.  count[i] = its record starts, starts[i *
+ * FC2_BAM_WALK_CAP + k] = the k-th one (ascending offsets into the block), exit[i] = the offset the walk
+ * leaves the block at (it may lie far past the block's end), FC2_BAM_WALK_NO_EXIT if it met a block_size
+ * below 32 or found no start.  A block whose status[i] != 0 is not read: count 0, no exit (status NULL:
+ * every block is read). */
+int fc2_bam_walk_launch(const uint8_t *slots, const uint32_t *isize, const uint32_t *status, uint16_t *starts,
+                        uint32_t *count, uint32_t *exit, uint32_t n_blocks, void *stream);
+/* The same for one block of n <= 65536 bytes in host memory, on the CPU: the ingest's own walk (what it
+ * runs for the blocks the CPU inflates), in the kernel's output form; starts holds FC2_BAM_WALK_CAP entries. */
+int fc2_bam_walk_host(const uint8_t *block, uint32_t n, uint16_t *starts, uint32_t *count, uint32_t *exit);
+/* Whether the blocks the GPU inflates take their record lists from the device as well (on != 0, the
+ * default) or are walked by host threads (0).  Holds from the next batch on; without a GPU inflate it
+ * changes nothing. */
+int fc2_ingest_set_gpu_walk(fc2_ingest *h, int on);
+/* Blocks of the batches the GPU inflated whose record lists came from the device, and those walked on the
+ * host (the blocks the device refused, or every block with the device lists off). */
+int fc2_ingest_walk_counts(const fc2_ingest *h, uint64_t *device_blocks, uint64_t *cpu_blocks);
 #ifdef __cplusplus
 }
 #endif

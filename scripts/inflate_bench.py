@@ -1,7 +1,9 @@
 """GPU BGZF inflate (csrc/fc2_inflate.hip) against the CPU on the CLI's BAM input: the blocks of
 scripts/gen_reads' BAM (fc2_sam_to_bam, zlib level 1) inflated by fc2_bgzf_inflate_launch in launches
 of --batch blocks (the ingest's batch) and in one launch of all, timed with HIP events on the launch
-stream, each block's CRC-32 checked on the device (and again here); the CPU leg is zlib on one core over the same blocks.  One JSON line.
+stream, each block's CRC-32 checked on the device (and again here); the CPU leg is zlib on one core over the same blocks.
+The walk leg times fc2_bam_walk_launch (the blocks' BAM record starts) over the same blocks, in the same
+launches, from the slots the inflate left, its lists checked against fc2_bam_walk_host.  One JSON line.
 Measurement infrastructure (not part of the product).
 
 usage: python scripts/inflate_bench.py [--reads N] [--batch B] [--reps R]
@@ -64,7 +66,17 @@ def main():
                                           t_isz[i0:].data_ptr(), t_crc[i0:].data_ptr(), dst[i0 * 65536:].data_ptr(),
                                           st[i0:].data_ptr(), i1 - i0, ctypes.c_void_p(stream.cuda_stream)))
 
-    def timed(step):
+    cap = N.BAM_WALK_CAP
+    w_starts = torch.empty(n * cap, dtype=torch.int16, device=dev)
+    w_count = torch.empty(n, dtype=torch.int32, device=dev)
+    w_exit = torch.empty(n, dtype=torch.int32, device=dev)
+
+    def walk(i0, i1):
+        N.check(L.fc2_bam_walk_launch(dst[i0 * 65536:].data_ptr(), t_isz[i0:].data_ptr(), st[i0:].data_ptr(),
+                                      w_starts[i0 * cap:].data_ptr(), w_count[i0:].data_ptr(), w_exit[i0:].data_ptr(),
+                                      i1 - i0, ctypes.c_void_p(stream.cuda_stream)))
+
+    def timed(step, launch=launch):
         best = None
         for _ in range(a.reps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -83,6 +95,18 @@ def main():
     out = dst.cpu().numpy()
     bad = sum(1 for i in range(n) if s[i] != 0 or zlib.crc32(out[i * 65536:i * 65536 + isz[i]].tobytes()) != crc[i])
     ms_all, ms_batch = timed(n), timed(a.batch)
+    # the walk over the inflated slots; every 97th block's lists against the CPU's walk
+    walk(0, n)
+    torch.cuda.synchronize()
+    wc, we = w_count.cpu().numpy().view(np.uint32), w_exit.cpu().numpy().view(np.uint32)
+    ws = w_starts.cpu().numpy().view(np.uint16).reshape(n, cap)
+    row, hc, he = np.zeros(cap, np.uint16), ctypes.c_uint32(), ctypes.c_uint32()
+    walk_bad = 0
+    for i in range(0, n, 97):
+        blk = np.ascontiguousarray(out[i * 65536:i * 65536 + isz[i]])
+        N.check(L.fc2_bam_walk_host(blk.ctypes.data, int(isz[i]), row.ctypes.data, ctypes.byref(hc), ctypes.byref(he)))
+        walk_bad += not (hc.value == wc[i] and he.value == we[i] and (row[:hc.value] == ws[i, :hc.value]).all())
+    wms_all, wms_batch = timed(n, walk), timed(a.batch, walk)
     total = int(isz.sum())
     # CPU: zlib on one core, about 2 s of it
     t0, done, k = time.time(), 0, 0
@@ -96,7 +120,12 @@ def main():
         "gpu_one_launch_ms": round(ms_all, 3), "gpu_one_launch_GBps": round(total / ms_all / 1e6, 2),
         "gpu_batch": a.batch, "gpu_batched_ms": round(ms_batch, 3),
         "gpu_batched_GBps": round(total / ms_batch / 1e6, 2),
-        "cpu_zlib_1core_GBps": round(done / cpu_s / 1e9, 3)}))
+        "cpu_zlib_1core_GBps": round(done / cpu_s / 1e9, 3),
+        "walk_records": int(wc.sum()), "walk_bad_blocks": int(walk_bad),
+        "walk_one_launch_ms": round(wms_all, 3), "walk_batched_ms": round(wms_batch, 3),
+        "walk_share_of_inflate_one_launch": round(wms_all / ms_all, 4),
+        "walk_share_of_inflate_batched": round(wms_batch / ms_batch, 4),
+        "walk_list_bytes_per_block": cap * 2 + 8}))
 
 
 if __name__ == "__main__":
