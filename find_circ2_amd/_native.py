@@ -156,6 +156,7 @@ EXPORTED = [
     "fc2_ingest_format", "fc2_sam_to_bam", "fc2_bgzf_inflate_launch",
     "fc2_ingest_set_gpu_inflate", "fc2_ingest_set_gpu_inflate_from", "fc2_ingest_inflate_counts",
     "fc2_bam_walk_launch", "fc2_bam_walk_host", "fc2_ingest_set_gpu_walk", "fc2_ingest_walk_counts",
+    "fc2_bam_digest_launch", "fc2_bam_digest_host", "fc2_ingest_set_gpu_digest", "fc2_ingest_digest_counts",
     # include/fc2_caller.h
     "fc2_caller_open", "fc2_caller_set_genome", "fc2_caller_inflate_counts", "fc2_caller_ingest", "fc2_caller_close", "fc2_caller_next",
     "fc2_caller_submit", "fc2_caller_submit_compact", "fc2_caller_submit_long", "fc2_caller_queued", "fc2_caller_take", "fc2_caller_rows", "fc2_caller_write_rows", "fc2_caller_counter", "fc2_caller_stats",
@@ -170,6 +171,16 @@ EXPORTED = [
 # include/fc2_ingest.h: entries of a block's row of record starts, and "the walk does not leave the block"
 BAM_WALK_CAP = 1824
 BAM_WALK_NO_EXIT = 0xFFFFFFFF
+# ... and the most blocks of one fc2_bam_digest_launch
+BAM_DIGEST_MAX_BLOCKS = 1024
+
+
+class BamDigest(ctypes.Structure):
+    """fc2_bam_digest: one record's derived fields (32 bytes)."""
+    _fields_ = [("state", ctypes.c_uint8), ("as_type", ctypes.c_uint8), ("xs_type", ctypes.c_uint8),
+                ("has_qual", ctypes.c_uint8), ("block_size", ctypes.c_uint32), ("astart", ctypes.c_int32),
+                ("qlen", ctypes.c_int32), ("as_bits", ctypes.c_uint32), ("xs_bits", ctypes.c_uint32),
+                ("aend", ctypes.c_int64)]
 
 
 class IngestParams(ctypes.Structure):
@@ -318,6 +329,10 @@ def lib() -> ctypes.CDLL:
         "fc2_bam_walk_host": (ctypes.c_int, [vp, u32, vp, P(u32), P(u32)]),
         "fc2_ingest_set_gpu_walk": (ctypes.c_int, [vp, ctypes.c_int]),
         "fc2_ingest_walk_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
+        "fc2_bam_digest_launch": (ctypes.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
+        "fc2_bam_digest_host": (ctypes.c_int, [vp, u32, u32, P(BamDigest)]),
+        "fc2_ingest_set_gpu_digest": (ctypes.c_int, [vp, ctypes.c_int]),
+        "fc2_ingest_digest_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "fc2_caller_inflate_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "fc2_ctx_create": (ctypes.c_int, [ctypes.c_int, P(vp)]),
         "fc2_ctx_create_sibling": (ctypes.c_int, [vp, P(vp)]),

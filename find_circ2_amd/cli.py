@@ -289,6 +289,13 @@ def _gpu_walk():
     return os.environ.get("FC2_GPU_WALK") != "0"
 
 
+def _gpu_digest():
+    """Whether that GPU also computes the listed records' derived fields for the parse threads (DESIGN.md §5
+    "Record digests from the device"): only with FC2_GPU_DIGEST=1 -- off by default, and off at 0 or any
+    other value -- since its effect on the loop has not been measured at 20M reads."""
+    return os.environ.get("FC2_GPU_DIGEST") == "1"
+
+
 def _gzip_device(options):
     """spliced_reads.fastq.gz compressed on the GPU: only with FC2_GPU_GZIP=1, on the first of
     the run's devices, in tiles of FC2_GPU_GZIP_TILE bytes (32768), waiting at most
@@ -322,7 +329,8 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                       write_multi=out.get("multi") is not None, genome_dummy=dummy,
                       known_circ=options.known_circ, known_lin=options.known_lin, bam_out=bam_path,
                       reads_gz=reads_gz,
-                      **(dict(zip(("inflate_device", "inflate_after"), _inflate_device(options)), gpu_walk=_gpu_walk())
+                      **(dict(zip(("inflate_device", "inflate_after"), _inflate_device(options)), gpu_walk=_gpu_walk(),
+                              gpu_digest=_gpu_digest())
                          if genome_eval is not None else {}),
                       **(_gzip_device(options) if genome_eval is not None and reads_gz else {}))
     try:

@@ -8,6 +8,8 @@
 
 #include <string>
 
+#include "../../include/fc2_ingest.h"
+
 namespace fc2 {
 namespace inf {
 
@@ -28,11 +30,15 @@ uint32_t gpu_max_blocks(const Gpu *g);
 // fc2_ingest.cpp's walk_block finds), downloaded with the bytes: after gpu_finish, gpu_walk(g, i, ...)
 // for a block with status 0 is its row of `count` ascending offsets into the block and the offset the
 // walk leaves the block at (FC2_BAM_WALK_NO_EXIT: nowhere).
-void gpu_begin(Gpu *g, char *dest, bool walk);
+// With digest (and walk), the listed records' digest rows (bam_digest_kernel, include/fc2_ingest.h) come
+// back too: after gpu_finish, gpu_digest(g, i, count) is block i's `count` rows, one per listed start
+// (nullptr: none -- a batch with a block over 64 KiB, or with more rows than the pinned buffer holds).
+void gpu_begin(Gpu *g, char *dest, bool walk, bool digest);
 bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, size_t i0, size_t i1);
 bool gpu_finish(Gpu *g, std::string &err);
 uint32_t gpu_status(const Gpu *g, size_t i);
 const uint16_t *gpu_walk(const Gpu *g, size_t i, uint32_t &count, uint32_t &exit);
+const fc2_bam_digest *gpu_digest(const Gpu *g, size_t i, uint32_t &count);
 
 // a pinned buffer of >= n bytes from the pool (nullptr: no pool, too large, or none left)
 void *pinned_take(size_t n);

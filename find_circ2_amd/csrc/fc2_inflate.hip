@@ -532,7 +532,204 @@ __global__ __launch_bounds__(64) void bam_walk_kernel(const uint8_t *__restrict_
     if (lane == 0) count[blk] = cnt, exit_at[blk] = ex;
 }
 
+// ---- the record digest: parse_bam_body's derived fields (fc2_ingest.cpp), on the device ------------
+// One wavefront per BGZF block, no LDS (it runs beside the inflate kernel's eight 20 KB workgroups a
+// CU); the lanes stride over the block's listed record starts, one record a lane.  A record is read
+// from the chunk's contiguous stream, not from the slots: it may run on through the following blocks.
+// The lanes' records differ in their CIGAR and tag counts, so the loops diverge, and a lane's loads
+// are its own (a record's bytes share cache lines with the neighbouring lanes' records: L2 takes the
+// re-reads); fields are composed from byte loads, since a record starts at any byte residue and the
+// stream itself at any address.
+//
+// Bounds.  Loads: dg_u8 / dg_u16 / dg_u32 are only called with offsets the caller has shown to be
+// below `lim`, the record's own end (at + 4 + block_size), after lim <= n_bytes was checked -- the
+// block_size itself after at + 4 <= n_bytes -- so every load is inside [bytes, bytes + n_bytes)
+// whatever the bytes say.  Loops: the CIGAR loop runs n_cigar_op <= 65535 times over words the field
+// check placed below lim; the tag loop advances at least 4 bytes a turn and the Z / H scan one byte a
+// turn, both towards lim <= n_bytes; the status loop visits each block once.  Stores: lane k of block
+// blk writes rows[first[blk] + k] with k < min(count[blk], cap), below first[blk + 1] <= first[n_blocks],
+// the launch's counted rows; first[blk] (and first[n_blocks], by the last block) by lane 0.
+
+constexpr uint32_t kDigestMaxBlocks = FC2_BAM_DIGEST_MAX_BLOCKS;
+static_assert(sizeof(fc2_bam_digest) == 32, "a digest row is 32 bytes");
+
+__device__ __forceinline__ uint32_t dg_u8(const uint8_t *__restrict__ b, uint64_t o) { return b[o]; }
+__device__ __forceinline__ uint32_t dg_u16(const uint8_t *__restrict__ b, uint64_t o) {
+    return dg_u8(b, o) | (dg_u8(b, o + 1) << 8);
+}
+__device__ __forceinline__ uint32_t dg_u32(const uint8_t *__restrict__ b, uint64_t o) {
+    return dg_u8(b, o) | (dg_u8(b, o + 1) << 8) | (dg_u8(b, o + 2) << 16) | (dg_u8(b, o + 3) << 24);
+}
+
+// an AS / XS value's bytes as its type says (the tag walk has checked that they lie below lim)
+__device__ __forceinline__ uint32_t dg_tag_bits(const uint8_t *__restrict__ b, uint64_t p, uint32_t ty) {
+    switch (ty) {
+        case 'c': return (uint32_t)(int32_t)(int8_t)dg_u8(b, p);
+        case 'C': return dg_u8(b, p);
+        case 's': return (uint32_t)(int32_t)(int16_t)dg_u16(b, p);
+        case 'S': return dg_u16(b, p);
+        case 'i': case 'I': case 'f': return dg_u32(b, p);
+        default: return 0;                      // A Z H B
+    }
+}
+
+// the row of the record start at byte `at` of the stream; false: state 0 (r.block_size may be set)
+__device__ bool digest_record(const uint8_t *__restrict__ bytes, uint32_t n_bytes, uint64_t at,
+                              const uint32_t *__restrict__ ooff, const uint32_t *__restrict__ status, uint32_t blk,
+                              uint32_t n_blocks, fc2_bam_digest &r) {
+    if (at + 4 > n_bytes) return false;
+    const uint32_t bs = dg_u32(bytes, at);
+    r.block_size = bs;
+    if (bs < 32u || bs >= (1u << 28)) return false;
+    const uint64_t b = at + 4, lim = b + bs;    // the record's body: [b, lim)
+    if (lim > n_bytes) return false;
+    if (status)                                 // every block it touches was inflated on the device
+        for (uint32_t j = blk; j < n_blocks && (j == blk || ooff[j] < lim); ++j)
+            if (status[j] != INF_OK) return false;
+    const int64_t pos = (int32_t)dg_u32(bytes, b + 4);
+    const uint32_t l_name = dg_u8(bytes, b + 8), n_cig = dg_u16(bytes, b + 12), flag = dg_u16(bytes, b + 14);
+    const int64_t l_seq = (int32_t)dg_u32(bytes, b + 16);
+    if (l_seq < 0 || 32 + (int64_t)l_name + 4 * (int64_t)n_cig + (l_seq + 1) / 2 + l_seq > (int64_t)bs) return false;
+    if (l_name == 0 || dg_u8(bytes, b + 32 + l_name - 1) != 0) return false;
+    // cigar_info: the reference span, the clips before the first M, the soft clips at both ends
+    uint64_t p = b + 32 + l_name;
+    uint64_t ref_span = 0, astart = 0, lead = 0, trail = 0;
+    bool stop = false, leading = true;
+    for (uint32_t k = 0; k < n_cig; ++k, p += 4) {
+        const uint32_t c = dg_u32(bytes, p), op = c & 0xFu, len = c >> 4;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_span += len;
+        if (!stop) {
+            if (op == 4 || op == 5) astart += len;
+            else if (op == 0) stop = true;
+        }
+        if (leading) {
+            if (op == 4) lead += len;
+            else if (op != 5) leading = false;
+        }
+        if (op == 4) trail += len;              // (the soft clips of the trailing run of S / H)
+        else if (op != 5) trail = 0;
+    }
+    if ((ref_span | astart | lead | trail) >> 31) return false;
+    r.astart = (int32_t)astart;
+    r.aend = ((flag & 4u) || n_cig == 0) ? -1 : pos + (int64_t)ref_span;
+    // finish_rec: len(seq[lead : len(seq) - trail]) with Python's slice semantics
+    if (l_seq > 0) {
+        const int64_t n = l_seq;
+        int64_t s0 = (int64_t)lead, e0 = n - (int64_t)trail;
+        if (e0 < 0) e0 += n;
+        s0 = s0 > n ? n : s0;
+        e0 = e0 < 0 ? 0 : (e0 > n ? n : e0);
+        r.qlen = (int32_t)(e0 > s0 ? e0 - s0 : 0);
+        r.has_qual = dg_u8(bytes, p + (uint64_t)(l_seq + 1) / 2) != 0xFFu;
+    } else {
+        r.qlen = -1;
+        r.has_qual = 0;
+    }
+    p += (uint64_t)(l_seq + 1) / 2 + (uint64_t)l_seq;
+    // scan_bam_tags / aux_value_size over [p, lim)
+    uint32_t n_as = 0, n_xs = 0;
+    while (p < lim) {
+        if (lim - p < 3) return false;
+        const uint32_t t0 = dg_u8(bytes, p), t1 = dg_u8(bytes, p + 1), ty = dg_u8(bytes, p + 2);
+        p += 3;
+        const uint64_t left = lim - p;
+        uint64_t n;
+        switch (ty) {
+            case 'c': case 'C': case 'A': n = 1; break;
+            case 's': case 'S': n = 2; break;
+            case 'i': case 'I': case 'f': n = 4; break;
+            case 'Z': case 'H': {
+                uint64_t z = p;
+                while (z < lim && dg_u8(bytes, z) != 0) ++z;
+                if (z == lim) return false;
+                n = z - p + 1;
+                break;
+            }
+            case 'B': {
+                if (left < 5) return false;
+                const uint32_t sub = dg_u8(bytes, p);
+                const uint32_t w = (sub == 'c' || sub == 'C') ? 1u : (sub == 's' || sub == 'S') ? 2u
+                                 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4u : 0u;
+                const int32_t cnt = (int32_t)dg_u32(bytes, p + 1);
+                if (!w || cnt < 0) return false;
+                n = 5 + (uint64_t)w * (uint32_t)cnt;
+                break;
+            }
+            default: return false;
+        }
+        if (n > left) return false;
+        const bool as = t0 == 'A' && t1 == 'S', xs = t0 == 'X' && t1 == 'S';
+        if (as) {
+            if (n_as++) return false;           // first and last would differ: the host's logic
+            r.as_type = (uint8_t)ty;
+            r.as_bits = dg_tag_bits(bytes, p, ty);
+        }
+        if (xs) {
+            if (n_xs++) return false;
+            r.xs_type = (uint8_t)ty;
+            r.xs_bits = dg_tag_bits(bytes, p, ty);
+        }
+        p += n;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(64) void bam_digest_kernel(const uint8_t *__restrict__ bytes, uint32_t n_bytes,
+                                                        const uint32_t *__restrict__ ooff, const uint32_t *__restrict__ status,
+                                                        const uint16_t *__restrict__ starts, const uint32_t *__restrict__ count,
+                                                        fc2_bam_digest *__restrict__ rows, uint32_t *__restrict__ first,
+                                                        uint32_t n_blocks) {
+    const uint32_t blk = blockIdx.x, lane = threadIdx.x;
+    // first[blk]: the rows of the blocks before this one, summed across the wave (n_blocks <= 1024:
+    // at most 16 counts a lane)
+    uint32_t f = 0;
+    for (uint32_t j = lane; j < blk; j += 64u) f += min(count[j], kWalkCap);
+    for (int d = 32; d; d >>= 1) f += __shfl_xor(f, d, 64);
+    const uint32_t cnt = min(count[blk], kWalkCap);
+    if (lane == 0) {
+        first[blk] = f;
+        if (blk + 1 == n_blocks) first[n_blocks] = f + cnt;
+    }
+    const uint16_t *row = starts + (uint64_t)blk * kWalkCap;
+    const uint32_t o0 = ooff[blk];
+    for (uint32_t k = lane; k < cnt; k += 64u) {
+        fc2_bam_digest r;
+        r.state = r.as_type = r.xs_type = r.has_qual = 0;
+        r.block_size = 0;
+        r.astart = r.qlen = 0;
+        r.as_bits = r.xs_bits = 0;
+        r.aend = 0;
+        if (digest_record(bytes, n_bytes, (uint64_t)o0 + row[k], ooff, status, blk, n_blocks, r)) {
+            r.state = 1;
+        } else {                                // the host parses it: block_size and zeros
+            const uint32_t bs = r.block_size;
+            r.as_type = r.xs_type = r.has_qual = 0;
+            r.astart = r.qlen = 0;
+            r.as_bits = r.xs_bits = 0;
+            r.aend = 0;
+            r.block_size = bs;
+        }
+        rows[(uint64_t)f + k] = r;
+    }
+}
+
 }  // namespace
+
+// C ABI (include/fc2_ingest.h): the digest rows of the record starts listed for n_blocks blocks
+extern "C" int fc2_bam_digest_launch(const uint8_t *bytes, uint32_t n_bytes, const uint32_t *ooff, const uint32_t *isize,
+                                     const uint32_t *status, const uint16_t *starts, const uint32_t *count,
+                                     fc2_bam_digest *rows, uint32_t *first, uint32_t n_blocks, void *stream) {
+    if (!n_blocks) return FC2_OK;
+    if ((!bytes && n_bytes) || !ooff || !isize || !starts || !count || !rows || !first)
+        return fc2::fail(FC2_E_PARAM, "fc2_bam_digest_launch: null argument");
+    if (n_blocks > kDigestMaxBlocks) return fc2::fail(FC2_E_PARAM, "fc2_bam_digest_launch: more than 1024 blocks");
+    if (((uintptr_t)rows & 7u) || ((uintptr_t)first & 3u))
+        return fc2::fail(FC2_E_PARAM, "fc2_bam_digest_launch: rows must be 8-byte and first 4-byte aligned");
+    hipLaunchKernelGGL(bam_digest_kernel, dim3(n_blocks), dim3(64), 0, (hipStream_t)stream, bytes, n_bytes, ooff, status,
+                       starts, count, rows, first, n_blocks);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_bam_digest_launch: ") + hipGetErrorString(e));
+}
 
 // C ABI (include/fc2_ingest.h): the record starts of n_blocks inflated blocks
 extern "C" int fc2_bam_walk_launch(const uint8_t *slots, const uint32_t *isize, const uint32_t *status, uint16_t *starts,
@@ -663,11 +860,24 @@ struct Gpu {
     hipStream_t stream[kStreams] = {};
     hipEvent_t done[kStreams] = {};            // blocking-sync: the reader thread sleeps, not spins
     uint8_t *h_src = nullptr, *d_src = nullptr, *d_slots = nullptr, *d_out = nullptr;
-    uint32_t *h_meta = nullptr, *d_meta = nullptr;      // off | len | isize | crc | ooff | status
+    uint32_t *h_meta = nullptr, *d_meta = nullptr;      // off | len | isize | crc | ooff | status | ooff in the chunk
     // the blocks' record lists (bam_walk_kernel): count | exit, and a row of starts per block
     uint32_t *h_walk = nullptr, *d_walk = nullptr;
     uint16_t *h_starts = nullptr, *d_starts = nullptr;
     bool walk = false;                         // this batch's blocks are listed on the device
+    // the listed records' digest rows (bam_digest_kernel), made by the first batch that asks for them:
+    // a chunk's rows lie dense from row i0 * kWalkCap of d_rows on, its first[] (c + 1 entries) at
+    // d_first + i0 + its index among the batch's chunks; gpu_finish downloads the counted rows into h_rows
+    fc2_bam_digest *d_rows = nullptr, *h_rows = nullptr;
+    uint32_t *d_first = nullptr, *h_first = nullptr;
+    size_t rows_cap = 0;                       // rows h_rows holds (a batch with more gets no digests)
+    struct Chunk {
+        uint32_t i0, c, foff;
+        int s;
+        uint64_t row0;                         // its first row in h_rows
+    };
+    std::vector<Chunk> dchunks;
+    bool digest = false, digest_ok = false, rows_ready = false;
     bool pooled = false;
     // the batch under way (gpu_begin .. gpu_finish)
     char *dest = nullptr;
@@ -690,7 +900,7 @@ Gpu *gpu_open(int device, uint32_t max_blocks, size_t pool_cap, std::string &err
     g->device = device;
     g->max_blocks = max_blocks;
     g->src_cap = (size_t)max_blocks * kOutMax + 64;      // a BGZF block is at most 64 KiB
-    const size_t out = (size_t)max_blocks * kOutMax, meta = (size_t)max_blocks * 6 * sizeof(uint32_t);
+    const size_t out = (size_t)max_blocks * kOutMax, meta = (size_t)max_blocks * 7 * sizeof(uint32_t);
     const size_t walk = (size_t)max_blocks * 2 * sizeof(uint32_t), rows = (size_t)max_blocks * kWalkCap * sizeof(uint16_t);
     bool ok = hip_ok(g, hipSetDevice(device), "hipSetDevice");
     for (int k = 0; k < kStreams && ok; ++k)
@@ -727,6 +937,10 @@ void gpu_close(Gpu *g) {
     if (hipSetDevice(g->device) == hipSuccess) {
         for (int k = 0; k < kStreams; ++k)
             if (g->stream[k]) (void)hipStreamSynchronize(g->stream[k]);
+        if (g->d_first) (void)hipFree(g->d_first);
+        if (g->d_rows) (void)hipFree(g->d_rows);
+        if (g->h_first) (void)hipHostFree(g->h_first);
+        if (g->h_rows) (void)hipHostFree(g->h_rows);
         if (g->d_starts) (void)hipFree(g->d_starts);
         if (g->d_walk) (void)hipFree(g->d_walk);
         if (g->h_starts) (void)hipHostFree(g->h_starts);
@@ -748,14 +962,31 @@ void gpu_close(Gpu *g) {
 
 uint32_t gpu_max_blocks(const Gpu *g) { return g->max_blocks; }
 
-void gpu_begin(Gpu *g, char *dest, bool walk) {
+// rows a block of the pinned row buffer: 64 KiB of records of 128 bytes or more
+constexpr size_t kRowsPerBlock = 512;
+
+void gpu_begin(Gpu *g, char *dest, bool walk, bool digest) {
     g->dest = dest;
     g->walk = walk;
+    g->digest = walk && digest;
+    g->digest_ok = g->digest;
+    g->rows_ready = false;
+    g->dchunks.clear();
     g->n = 0;
     g->out = 0;
     g->chunks = 0;
     g->ok = hipSetDevice(g->device) == hipSuccess;
     g->err = g->ok ? "" : "GPU inflate: hipSetDevice failed";
+    if (g->ok && g->digest && !g->d_rows) {
+        const size_t M = g->max_blocks;
+        g->rows_cap = M * kRowsPerBlock;
+        hip_ok(g, hipMalloc((void **)&g->d_rows, M * kWalkCap * sizeof(fc2_bam_digest)), "device digest rows") &&
+            hip_ok(g, hipMalloc((void **)&g->d_first, (2 * M + 1) * sizeof(uint32_t)), "device row index") &&
+            hip_ok(g, hipHostMalloc((void **)&g->h_rows, g->rows_cap * sizeof(fc2_bam_digest), hipHostMallocDefault),
+                   "pinned digest rows") &&
+            hip_ok(g, hipHostMalloc((void **)&g->h_first, (2 * M + 1) * sizeof(uint32_t), hipHostMallocDefault),
+                   "pinned row index");
+    }
 }
 
 bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, size_t i0, size_t i1) {
@@ -767,7 +998,8 @@ bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, 
         return false;
     }
     const uint32_t M = g->max_blocks;
-    uint32_t *off = g->h_meta, *len = off + M, *isz = len + M, *crc = isz + M, *ooff = crc + M, *st = ooff + M;
+    uint32_t *off = g->h_meta, *len = off + M, *isz = len + M, *crc = isz + M, *ooff = crc + M, *st = ooff + M,
+             *rooff = st + M;
     // the chunk's bytes into the pinned input (at their offsets in the batch), 8 zero bytes behind
     const size_t b0 = boff[i0], b1 = boff[i1 - 1] + bsz[i1 - 1];
     memcpy(g->h_src + b0, raw + b0, b1 - b0);
@@ -782,6 +1014,7 @@ bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, 
         crc[i] = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
         isz[i] = t[4] | (t[5] << 8) | (t[6] << 16) | ((uint32_t)t[7] << 24);
         ooff[i] = (uint32_t)g->out;
+        rooff[i] = ooff[i] - ooff[i0];
         if (isz[i] > kOutMax) fits = false;
         g->out += std::min<uint32_t>(isz[i], kOutMax);
     }
@@ -789,6 +1022,7 @@ bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, 
     const uint32_t c = (uint32_t)(i1 - i0);
     if (!fits) {                               // not BGZF: the CPU inflates (and reports) these blocks
         for (size_t i = i0; i < i1; ++i) st[i] = INF_TOO_BIG;
+        g->digest_ok = false;                  // (the host's offsets differ from the device's from here on)
         return true;
     }
     hipStream_t s = g->stream[g->chunks++ % kStreams];
@@ -823,6 +1057,23 @@ bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, 
              hip_ok(g, hipMemcpyAsync(g->h_walk + M + i0, g->d_walk + M + i0, c * w, hipMemcpyDeviceToHost, s), "download");
         if (!ok) return false;
     }
+    if (g->digest && g->digest_ok && c <= kDigestMaxBlocks) {
+        // the listed records' digest rows, from the chunk's contiguous bytes (records cross blocks)
+        Gpu::Chunk ch{(uint32_t)i0, c, (uint32_t)(i0 + g->dchunks.size()), (int)((g->chunks - 1) % kStreams), 0};
+        uint32_t *d_rooff = d_st + M;
+        ok = hip_ok(g, hipMemcpyAsync(d_rooff + i0, rooff + i0, c * w, hipMemcpyHostToDevice, s), "upload");
+        if (ok && fc2_bam_digest_launch(g->d_out + o0, (uint32_t)(g->out - o0), d_rooff + i0, d_isz + i0, d_st + i0,
+                                        g->d_starts + (size_t)i0 * kWalkCap, g->d_walk + i0,
+                                        g->d_rows + (size_t)i0 * kWalkCap, g->d_first + ch.foff, c, s) != FC2_OK) {
+            if (g->ok) g->err = "GPU inflate: record digest launch failed";
+            g->ok = false;
+            return false;
+        }
+        ok = ok && hip_ok(g, hipMemcpyAsync(g->h_first + ch.foff, g->d_first + ch.foff, (c + 1) * w, hipMemcpyDeviceToHost, s),
+                          "download");
+        if (!ok) return false;
+        g->dchunks.push_back(ch);
+    }
     return hip_ok(g, hipMemcpyAsync(g->dest + o0, g->d_out + o0, g->out - o0, hipMemcpyDeviceToHost, s), "download") &&
            hip_ok(g, hipMemcpyAsync(st + i0, d_st + i0, c * w, hipMemcpyDeviceToHost, s), "download");
 }
@@ -830,6 +1081,28 @@ bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, 
 bool gpu_finish(Gpu *g, std::string &err) {
     for (int k = 0; k < kStreams; ++k)
         if (hip_ok(g, hipEventRecord(g->done[k], g->stream[k]), "event")) hip_ok(g, hipEventSynchronize(g->done[k]), "kernel");
+    // the digest rows, now that every chunk's first[] says how many there are: a sized download per
+    // chunk on its stream, side by side, then the same wait again
+    if (g->ok && g->digest && g->digest_ok && !g->dchunks.empty()) {
+        uint64_t total = 0;
+        for (Gpu::Chunk &ch : g->dchunks) {
+            ch.row0 = total;
+            total += std::min<uint64_t>(g->h_first[ch.foff + ch.c], (uint64_t)ch.c * kWalkCap);
+        }
+        if (total <= g->rows_cap) {
+            bool used[kStreams] = {};
+            for (const Gpu::Chunk &ch : g->dchunks) {
+                const uint64_t n = std::min<uint64_t>(g->h_first[ch.foff + ch.c], (uint64_t)ch.c * kWalkCap);
+                if (n && hip_ok(g, hipMemcpyAsync(g->h_rows + ch.row0, g->d_rows + (size_t)ch.i0 * kWalkCap,
+                                                  n * sizeof(fc2_bam_digest), hipMemcpyDeviceToHost, g->stream[ch.s]), "download"))
+                    used[ch.s] = true;
+            }
+            for (int k = 0; k < kStreams; ++k)
+                if (used[k] && hip_ok(g, hipEventRecord(g->done[k], g->stream[k]), "event"))
+                    hip_ok(g, hipEventSynchronize(g->done[k]), "download");
+            g->rows_ready = g->ok;
+        }
+    }
     if (!g->ok) err = g->err;
     return g->ok;
 }
@@ -840,6 +1113,20 @@ const uint16_t *gpu_walk(const Gpu *g, size_t i, uint32_t &count, uint32_t &exit
     count = std::min<uint32_t>(g->h_walk[i], kWalkCap);
     exit = g->h_walk[(size_t)g->max_blocks + i];
     return g->h_starts + i * kWalkCap;
+}
+
+const fc2_bam_digest *gpu_digest(const Gpu *g, size_t i, uint32_t &count) {
+    count = 0;
+    if (!g->rows_ready) return nullptr;
+    for (const Gpu::Chunk &ch : g->dchunks)
+        if (i >= ch.i0 && i < ch.i0 + ch.c) {
+            const uint32_t *f = g->h_first + ch.foff;
+            const uint32_t a = f[i - ch.i0], b = f[i - ch.i0 + 1];
+            if (a > b || b > f[ch.c] || (uint64_t)f[ch.c] > (uint64_t)ch.c * kWalkCap) return nullptr;
+            count = b - a;
+            return g->h_rows + ch.row0 + a;
+        }
+    return nullptr;
 }
 
 }  // namespace inf

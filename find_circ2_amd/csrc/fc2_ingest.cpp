@@ -47,8 +47,9 @@ namespace {
 
 // CIGAR helpers ------------------------------------------------------------
 struct CigarInfo {
-    int64_t ref_span = 0;
-    int32_t astart = 0, lead_s = 0, trail_s = 0;
+    // (64-bit sums: 65535 operations of up to 2^28 - 1 each; fc2_bam_digest_host tells from them which
+    // records the 32-bit fields below cannot hold)
+    int64_t ref_span = 0, astart = 0, lead_s = 0, trail_s = 0;
     bool any = false;
 };
 
@@ -83,7 +84,7 @@ int cig_code(char c) {
 
 void finish_rec(Rec &r, const std::vector<std::pair<int, int>> &ops, int64_t seqlen) {
     CigarInfo c = cigar_info(ops);
-    r.astart = c.astart;
+    r.astart = (int32_t)c.astart;
     r.aend = (r.unmapped() || !c.any) ? -1 : r.pos + c.ref_span;
     // len(seq[lead_s : len(seq) - trail_s]) with Python slice semantics (pysam's query when the
     // clips exceed SEQ: an empty string, or a negative end counted from the back)
@@ -210,7 +211,13 @@ struct RecLists {
     std::vector<size_t> ooff;                   // block k's bytes: [ooff[k], ooff[k + 1])
     std::vector<std::vector<uint32_t>> starts;
     std::vector<uint64_t> exit;
+    // the batch was inflated on the GPU; and, with fc2_ingest_set_gpu_digest, the device's digest of
+    // the record at starts[k][m]: rows[row0[k] + m] (row0[k] == kNoRows: block k has none)
+    bool gpu = false;
+    std::vector<fc2_bam_digest> rows;
+    std::vector<uint64_t> row0;
 };
+constexpr uint64_t kNoRows = ~uint64_t(0);
 
 struct BgzfBatch {
     CharBuf out;                 // kHead bytes of headroom, then the inflated bytes
@@ -289,6 +296,11 @@ struct GpuInflate {
     // blocks listed there, and those left to the host threads (of the batches the GPU took)
     std::atomic<bool> walk{true};
     std::atomic<uint64_t> walk_dev_blocks{0}, walk_cpu_blocks{0};
+    // fc2_ingest_set_gpu_digest: the listed records' derived fields (fc2_bam_digest rows) come from the
+    // device as well (bam_digest_kernel) and the parse threads take them instead of decoding CIGAR and
+    // tags; the records that did, and those the parse threads parsed (of the batches the GPU took)
+    std::atomic<bool> digest{false};
+    std::atomic<uint64_t> digest_dev_records{0}, digest_host_records{0};
     // FC2_CALLER_TIMING: the batch reader's time reading, submitting chunks, waiting for the device,
     // inflating refused blocks; batches whose buffer was pinned (downloaded into directly)
     int64_t read_ns = 0, add_ns = 0, wait_ns = 0, cpu_ns = 0;
@@ -315,10 +327,12 @@ struct GpuInflate {
         if (getenv("FC2_CALLER_TIMING") && batches)
             fprintf(stderr, "gpu inflate: %d batches (%d pinned), %llu blocks on the GPU, %llu on the CPU; reader s: "
                     "read %.3f submit %.3f wait %.3f cpu %.3f\n"
-                    "gpu walk: record lists of %llu blocks from the device, %llu walked on the host\n", batches, pinned,
+                    "gpu walk: record lists of %llu blocks from the device, %llu walked on the host\n"
+                    "gpu digest: %llu records' fields from the device, %llu parsed on the host\n", batches, pinned,
                     (unsigned long long)gpu_blocks.load(), (unsigned long long)cpu_blocks.load(), (read_ns - add_ns) * 1e-9,
                     add_ns * 1e-9, wait_ns * 1e-9, cpu_ns * 1e-9, (unsigned long long)walk_dev_blocks.load(),
-                    (unsigned long long)walk_cpu_blocks.load());
+                    (unsigned long long)walk_cpu_blocks.load(), (unsigned long long)digest_dev_records.load(),
+                    (unsigned long long)digest_host_records.load());
         if (opening.valid()) g = opening.get().first;
         fc2::inf::gpu_close(g);
     }
@@ -350,6 +364,7 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
     }
     gpu = gpu && gi->g;
     const bool dev_lists = gpu && gi->walk.load();
+    const bool dev_digest = dev_lists && gi->digest.load();
     size_t submitted = 0;
     auto submit = [&](bool last) {             // blocks read so far, in chunks of kGpuChunk
         if (!gpu) return;
@@ -363,7 +378,7 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
     const int64_t t0 = now_ns();
     if (gpu) {
         B.out.resize(kHead + (size_t)max_blocks * 65536);
-        fc2::inf::gpu_begin(gi->g, B.out.data() + kHead, dev_lists);
+        fc2::inf::gpu_begin(gi->g, B.out.data() + kHead, dev_lists, dev_digest);
         gi->batches += 1;
         gi->pinned += fc2::inf::pinned_owns(B.out.data());
     }
@@ -436,6 +451,7 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
         R->ooff = ooff;
         R->starts.resize(nb);
         R->exit.assign(nb, kNoExit);
+        R->gpu = on_gpu;
     }
     // ... or, for the blocks the device inflated, by the device: its rows, moved to batch offsets
     const bool listed = R && on_gpu && dev_lists;
@@ -449,6 +465,17 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
             st.resize(cnt);
             for (uint32_t k = 0; k < cnt; ++k) st[k] = (uint32_t)ooff[i] + row[k];
             R->exit[i] = ex == FC2_BAM_WALK_NO_EXIT ? kNoExit : ooff[i] + (uint64_t)ex;
+        }
+        if (dev_digest) {                       // the rows of the listed starts, block after block
+            R->row0.assign(nb, kNoRows);
+            for (size_t i = 0; i < nb; ++i) {
+                if (on_cpu[i]) continue;
+                uint32_t cnt;
+                const fc2_bam_digest *rows = fc2::inf::gpu_digest(gi->g, i, cnt);
+                if (!rows || cnt != R->starts[i].size()) continue;
+                R->row0[i] = R->rows.size();
+                R->rows.insert(R->rows.end(), rows, rows + cnt);
+            }
         }
     }
     std::atomic<size_t> next{0};
@@ -522,6 +549,7 @@ struct fc2_ingest {
     std::future<BgzfBatch> bgzf_next;
     std::shared_ptr<GpuInflate> gpu_inflate;     // fc2_ingest_set_gpu_inflate (null: the CPU inflates)
     bool gpu_walk = true;                        // fc2_ingest_set_gpu_walk, for a GPU inflate set later
+    bool gpu_digest = false;                     // fc2_ingest_set_gpu_digest, likewise
     std::atomic<int64_t> inflate_wait_ns{0};     // the reader's wait for inflated BGZF batches (timing)
     std::string z_err;
     // header
@@ -582,6 +610,10 @@ struct fc2_ingest::SamAhead {
         // or, BGZF input (bgzf_split_loop): whole records in place in an inflated batch
         std::shared_ptr<const CharBuf> vbuf;
         size_t voff = 0, vlen = 0;
+        // ... with the inflated batch's record lists (and digest rows), whose offsets count from byte
+        // lbase of vbuf (null: none; the bytes before lbase are the previous batch's)
+        std::shared_ptr<RecLists> lists;
+        size_t lbase = 0;
         std::vector<Rec> recs;
         size_t n = 0;
         int rc = FC2_OK;
@@ -987,7 +1019,14 @@ void append_bam_tags(std::string &t, const uint8_t *p, const uint8_t *end) {
 
 // AS / XS from binary BAM tags, as pysam's get_tag returns them (fc2::ing::PyNum); false when the
 // aux data is corrupt (aux_value_size) or ends inside a tag
-bool scan_bam_tags(Rec &r, const uint8_t *p, const uint8_t *end) {
+// (note, optional: the AS / XS tags' BAM types -- the first occurrence's -- and how often each occurs)
+struct TagNote {
+    uint8_t as_type = 0, xs_type = 0;
+    uint32_t n_as = 0, n_xs = 0;
+    uint32_t as_f = 0, xs_f = 0;                // an 'f' value's stored bits (a NaN's payload does not survive the double)
+};
+
+bool scan_bam_tags(Rec &r, const uint8_t *p, const uint8_t *end, TagNote *note = nullptr) {
     using fc2::ing::PyNum;
     while (p < end) {
         if (end - p < 3) return false;
@@ -1013,6 +1052,14 @@ bool scan_bam_tags(Rec &r, const uint8_t *p, const uint8_t *end) {
             if (xs && !r.has_xs) { r.has_xs = true; r.xs = v; }
             if (as) r.as_last = v;
             if (xs) r.xs_last = v;
+            if (note && as && !note->n_as++) {
+                note->as_type = (uint8_t)ty;
+                if (ty == 'f') memcpy(&note->as_f, p, 4);
+            }
+            if (note && xs && !note->n_xs++) {
+                note->xs_type = (uint8_t)ty;
+                if (ty == 'f') memcpy(&note->xs_f, p, 4);
+            }
         }
         p += adv;
     }
@@ -1023,8 +1070,55 @@ bool scan_bam_tags(Rec &r, const uint8_t *p, const uint8_t *end) {
 // header's reference names), so parser threads can call it.  ops: CIGAR scratch.  A record whose
 // fields do not fit its block, with an unterminated query name or corrupt aux data is an error, as
 // in htslib's bam_read1 / aux parsing.
+// A tag value from its BAM type and the bits of a digest row (fc2_bam_digest), as scan_bam_tags makes it
+fc2::ing::PyNum digest_tag(uint8_t ty, uint32_t bits) {
+    using fc2::ing::PyNum;
+    switch (ty) {
+        case 'c': case 's': case 'i': return PyNum::of_int((int32_t)bits);
+        case 'C': case 'S': case 'I': return PyNum::of_int((int64_t)bits);
+        case 'f': { float x; memcpy(&x, &bits, 4); return PyNum::of_float(x); }
+        case 'B': return PyNum::other(PyNum::ARRAY);
+        default: return PyNum::other(PyNum::STR);                      // A Z H
+    }
+}
+
+// With `row` -- the record's digest from the device (state 1, its block_size the record's; the device
+// has made every check below on the same bytes) and no SAM text wanted -- the derived fields are the
+// row's: only the name, the lazy SEQ / QUAL pointers and the fixed fields are read from the record.
+// `note`: see scan_bam_tags.
 int parse_bam_body(const fc2_ingest *h, const uint8_t *b, int32_t bs, Rec &r,
-                   std::vector<std::pair<int, int>> &ops, bool need_text, bool keep_raw, bool lazy = false) {
+                   std::vector<std::pair<int, int>> &ops, bool need_text, bool keep_raw, bool lazy = false,
+                   const fc2_bam_digest *row = nullptr, TagNote *note = nullptr) {
+    if (row && !need_text) {
+        int32_t ref_id, pos, l_seq;
+        uint16_t n_cig, flag;
+        const uint8_t l_name = b[8];
+        memcpy(&ref_id, b, 4); memcpy(&pos, b + 4, 4); memcpy(&n_cig, b + 12, 2); memcpy(&flag, b + 14, 2);
+        memcpy(&l_seq, b + 16, 4);
+        if (keep_raw) r.raw.assign((const char *)b - 4, 4 + (size_t)bs);
+        const uint8_t *p = b + 32;
+        r.qname.assign((const char *)p, l_name - 1);
+        p += (size_t)l_name + 4 * (size_t)n_cig;
+        r.lz.seq = (const char *)p;
+        r.lz.qual = (const char *)p + (l_seq + 1) / 2;
+        r.lz.n_seq = l_seq;
+        r.lz.bam = true;
+        r.has_seq = l_seq > 0;
+        r.has_qual = row->has_qual != 0;
+        r.seq_n = r.has_seq ? (uint32_t)l_seq : 1u;
+        if (!lazy) r.decode_lazy();
+        r.flag = flag;
+        r.tid = ref_id;
+        r.pos = pos;
+        r.astart = row->astart;
+        r.aend = row->aend;
+        r.qlen = row->qlen;
+        r.has_as = row->as_type != 0;
+        r.has_xs = row->xs_type != 0;
+        r.as = r.as_last = r.has_as ? digest_tag(row->as_type, row->as_bits) : fc2::ing::PyNum();
+        r.xs = r.xs_last = r.has_xs ? digest_tag(row->xs_type, row->xs_bits) : fc2::ing::PyNum();
+        return FC2_OK;
+    }
     if (bs < 32) return fc2::fail(FC2_E_FORMAT, "invalid BAM record (block shorter than its fixed fields)");
     const uint8_t *e = b + bs;
     int32_t ref_id, pos, l_seq, nref, npos, tlen;
@@ -1063,7 +1157,7 @@ int parse_bam_body(const fc2_ingest *h, const uint8_t *b, int32_t bs, Rec &r,
     finish_rec(r, ops, l_seq);
     r.has_as = r.has_xs = false;
     r.as = r.xs = r.as_last = r.xs_last = fc2::ing::PyNum();
-    if (!scan_bam_tags(r, p, e)) return fc2::fail(FC2_E_FORMAT, "corrupted aux data in a BAM record");
+    if (!scan_bam_tags(r, p, e, note)) return fc2::fail(FC2_E_FORMAT, "corrupted aux data in a BAM record");
     if (!need_text) return FC2_OK;
     const std::string &seq = r.seq, &qual = r.qual;
     std::string cig;
@@ -1370,6 +1464,7 @@ void bgzf_split_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
         b->block.clear();
         b->vbuf.reset();
         b->voff = b->vlen = 0;
+        b->lists.reset();
         auto truncated = [&]() {
             b->read_rc = FC2_E_FORMAT;
             b->read_err = "truncated BAM record" + (h->z_err.empty() ? "" : " (" + h->z_err + ")");
@@ -1417,6 +1512,8 @@ void bgzf_split_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
                 b->vbuf = cur;
                 b->voff = beg;
                 b->vlen = q - beg;
+                b->lists = lists;
+                b->lbase = base;
                 beg = q;
                 break;
             }
@@ -1461,16 +1558,45 @@ void sam_parse_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
         }
         const char *p = b->vbuf ? b->vbuf->data() + b->voff : b->block.data();
         const char *end = p + (b->vbuf ? b->vlen : b->block.size());
+        // the device's digest rows of a GPU-inflated batch: a cursor (BGZF block lj, its listed start
+        // lk) steps through the lists beside the records, whose offsets only grow; a record takes its
+        // row where a listed start is its own offset, the row is valid and carries its block_size
+        const RecLists *L = b->vbuf && h->bam ? b->lists.get() : nullptr;
+        const bool rows = L && !L->rows.empty() && !h->need_text;
+        const char *lorg = rows ? b->vbuf->data() + b->lbase : nullptr;
+        size_t lj = 0, lk = 0;
+        uint64_t dig_dev = 0, dig_host = 0;
         while (h->bam && p < end && b->rc == FC2_OK) {     // whole BAM records (bam/bgzf_split_loop)
             int32_t bs;
             memcpy(&bs, p, 4);
             if (b->n == b->recs.size()) b->recs.emplace_back();
+            const fc2_bam_digest *row = nullptr;
+            if (rows && p >= lorg && (size_t)(p - lorg) < L->n) {
+                const size_t bq = (size_t)(p - lorg);
+                const size_t nbk = L->starts.size();
+                if (bq < L->ooff[lj] || bq >= L->ooff[lj + 1]) {
+                    if (lj + 1 < nbk && bq >= L->ooff[lj + 1] && bq < L->ooff[lj + 2]) ++lj;
+                    else lj = (size_t)(std::upper_bound(L->ooff.begin(), L->ooff.end(), bq) - L->ooff.begin()) - 1;
+                    lk = 0;
+                }
+                const std::vector<uint32_t> &S = L->starts[lj];
+                if (lk < S.size() && S[lk] > bq) lk = 0;    // (never on a chain of growing offsets)
+                while (lk < S.size() && S[lk] < bq) ++lk;
+                if (lk < S.size() && S[lk] == bq && L->row0[lj] != kNoRows) {
+                    const fc2_bam_digest *c = &L->rows[L->row0[lj] + lk];
+                    if (c->state == 1 && c->block_size == (uint32_t)bs) row = c;
+                }
+            }
             const int rc = parse_bam_body(h, (const uint8_t *)p + 4, bs, b->recs[b->n], ps.ops, h->need_text, false,
-                                          !h->need_text);
+                                          !h->need_text, row);
             if (rc) { b->rc = rc; b->err = fc2_last_error(); break; }
             ++b->n;
             p += 4 + (size_t)bs;
+            if (L && L->gpu) ++(row ? dig_dev : dig_host);
         }
+        if (dig_dev | dig_host)
+            if (GpuInflate *gi = h->gpu_inflate.get()) gi->digest_dev_records += dig_dev, gi->digest_host_records += dig_host;
+        b->lists.reset();
         while (!h->bam && p < end && b->rc == FC2_OK) {
             const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
             const char *ls = p, *le = nl ? nl : end;
@@ -1957,6 +2083,7 @@ extern "C" int fc2_ingest_set_gpu_inflate_from(fc2_ingest *h, int device, uint64
     auto gi = std::make_shared<GpuInflate>();
     gi->device = device;
     gi->walk = h->gpu_walk;
+    gi->digest = h->gpu_digest;
     // batches of 1024 blocks (64 MiB inflated, four chunks of 256; fc2_inflate.hip) once the GPU
     // inflates; FC2_BGZF_BATCH still rules
     gi->max_blocks = getenv("FC2_BGZF_BATCH") ? (uint32_t)h->bgzf_blocks : 1024u;
@@ -1990,6 +2117,7 @@ extern "C" int fc2_ingest_set_gpu_inflate(fc2_ingest *h, int device, int wait) {
     auto gi = std::make_shared<GpuInflate>();
     gi->device = device;
     gi->walk = h->gpu_walk;
+    gi->digest = h->gpu_digest;
     gi->max_blocks = getenv("FC2_BGZF_BATCH") ? (uint32_t)h->bgzf_blocks : 1024u;
     gi->launch(true);
     auto r = gi->opening.get();
@@ -2019,6 +2147,54 @@ extern "C" int fc2_ingest_walk_counts(const fc2_ingest *h, uint64_t *device_bloc
     const GpuInflate *gi = h->gpu_inflate.get();
     if (device_blocks) *device_blocks = gi ? gi->walk_dev_blocks.load() : 0;
     if (cpu_blocks) *cpu_blocks = gi ? gi->walk_cpu_blocks.load() : 0;
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_set_gpu_digest(fc2_ingest *h, int on) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_digest: null argument");
+    h->gpu_digest = on != 0;
+    if (GpuInflate *gi = h->gpu_inflate.get()) gi->digest = on != 0;    // (the batch reader may be running: atomic)
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_digest_counts(const fc2_ingest *h, uint64_t *device_records, uint64_t *host_records) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_digest_counts: null argument");
+    const GpuInflate *gi = h->gpu_inflate.get();
+    if (device_records) *device_records = gi ? gi->digest_dev_records.load() : 0;
+    if (host_records) *host_records = gi ? gi->digest_host_records.load() : 0;
+    return FC2_OK;
+}
+
+// The digest row of one record start, from parse_bam_body itself (the form of the device's rows,
+// fc2_bam_digest_launch): what the parser leaves in a Rec, the tags' types and counts from
+// scan_bam_tags' note, and cigar_info's 64-bit sums for the records whose sums the row cannot hold
+extern "C" int fc2_bam_digest_host(const uint8_t *bytes, uint32_t n_bytes, uint32_t at, fc2_bam_digest *row) {
+    if ((!bytes && n_bytes) || !row) return fc2::fail(FC2_E_PARAM, "fc2_bam_digest_host: null argument");
+    if (at > n_bytes) return fc2::fail(FC2_E_RANGE, "fc2_bam_digest_host: the record start lies past the bytes");
+    memset(row, 0, sizeof *row);
+    if (n_bytes - at < 4) return FC2_OK;
+    uint32_t bs;
+    memcpy(&bs, bytes + at, 4);
+    row->block_size = bs;
+    if (bs < 32 || bs >= (1u << 28) || (uint64_t)at + 4 + bs > n_bytes) return FC2_OK;
+    Rec r;
+    std::vector<std::pair<int, int>> ops;
+    TagNote note;
+    if (parse_bam_body(nullptr, bytes + at + 4, (int32_t)bs, r, ops, false, false, true, nullptr, &note)) return FC2_OK;
+    const CigarInfo c = cigar_info(ops);
+    if (note.n_as > 1 || note.n_xs > 1 || ((c.ref_span | c.astart | c.lead_s | c.trail_s) >> 31)) return FC2_OK;
+    auto bits = [](uint8_t ty, uint32_t f, const fc2::ing::PyNum &v) -> uint32_t {
+        return ty == 'f' ? f : v.k == fc2::ing::PyNum::INT ? (uint32_t)v.i : 0u;
+    };
+    row->state = 1;
+    row->as_type = note.as_type;
+    row->xs_type = note.xs_type;
+    row->has_qual = r.has_qual;
+    row->astart = r.astart;
+    row->qlen = r.qlen;
+    row->as_bits = r.has_as ? bits(note.as_type, note.as_f, r.as) : 0;
+    row->xs_bits = r.has_xs ? bits(note.xs_type, note.xs_f, r.xs) : 0;
+    row->aend = r.aend;
     return FC2_OK;
 }
 

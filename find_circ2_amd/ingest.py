@@ -81,6 +81,19 @@ class NativeIngest:
         N.check(N.lib().fc2_ingest_walk_counts(self.h, ctypes.byref(d), ctypes.byref(c)))
         return int(d.value), int(c.value)
 
+    def set_gpu_digest(self, on: bool):
+        """Whether the parse threads take the derived fields (CIGAR sums, AS / XS, has-QUAL) of the records
+        the GPU inflated and listed from the device's digest rows (fc2_ingest_set_gpu_digest) or parse every
+        record themselves (the default); needs the device lists, holds from the next batch on."""
+        N.check(N.lib().fc2_ingest_set_gpu_digest(self.h, int(bool(on))))
+
+    def digest_counts(self) -> Tuple[int, int]:
+        """(records whose fields came from device rows, records the host parsed) of the batches the GPU
+        inflated."""
+        d, c = ctypes.c_uint64(), ctypes.c_uint64()
+        N.check(N.lib().fc2_ingest_digest_counts(self.h, ctypes.byref(d), ctypes.byref(c)))
+        return int(d.value), int(c.value)
+
     def close_bam_out(self):
         N.check(N.lib().fc2_ingest_close_bam_out(self.h))
 

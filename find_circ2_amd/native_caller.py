@@ -73,7 +73,8 @@ class NativeCaller:
     def __init__(self, path: str, is_bam: bool, copts, genome_names, fasta_handle=None, write_reads=True,
                  write_multi=True, genome_dummy=False, known_circ: str = "", known_lin: str = "",
                  bam_out: str = "", reads_gz=None, inflate_device=None, inflate_after: int = 0,
-                 gzip_device=None, gzip_tile: int = 0, gzip_timeout_s: float = 0.0, gpu_walk: bool = True):
+                 gzip_device=None, gzip_tile: int = 0, gzip_timeout_s: float = 0.0, gpu_walk: bool = True,
+                 gpu_digest: bool = False):
         o = copts
         # the strings must outlive the handle's open call (fc2_caller_open copies them)
         self._keep = [o.name.encode(), known_circ.encode() if known_circ else None,
@@ -95,6 +96,7 @@ class NativeCaller:
         self.inflate_device = inflate_device   # a BGZF input's blocks inflated on this GPU (None: the CPU)
         self.inflate_after = inflate_after     # ... once this many bytes of the input were read
         self.gpu_walk = gpu_walk               # ... their BAM record starts listed there too (else by host threads)
+        self.gpu_digest = gpu_digest           # ... and the listed records' derived fields computed there (else parsed)
         self.gzip_device = gzip_device         # spliced_reads.fastq.gz compressed on this GPU (None: the worker threads)
         self.gzip_tile = gzip_tile             # ... in tiles of this many bytes (0: 32768), each a gzip member
         self.gzip_timeout_s = gzip_timeout_s   # ... waiting at most this long for the device (0: 60 s)
@@ -117,6 +119,7 @@ class NativeCaller:
         if self.inflate_device is not None:
             N.check(L.fc2_ingest_set_gpu_inflate_from(ing, int(self.inflate_device), int(self.inflate_after)))
             N.check(L.fc2_ingest_set_gpu_walk(ing, int(bool(self.gpu_walk))))
+            N.check(L.fc2_ingest_set_gpu_digest(ing, int(bool(self.gpu_digest))))
         if self.reads_gz:
             path, level, threads, piece = self.reads_gz
             N.check(L.fc2_caller_set_reads_gz(self.h, path.encode(), int(level), int(threads), int(piece)))
@@ -147,6 +150,14 @@ class NativeCaller:
         g, c = ctypes.c_uint64(), ctypes.c_uint64()
         N.check(N.lib().fc2_caller_inflate_counts(self.h, ctypes.byref(g), ctypes.byref(c)))
         return int(g.value), int(c.value)
+
+    def digest_counts(self):
+        """(records whose derived fields came from the device's digest rows, records the host parsed) of
+        the batches the GPU inflated (fc2_ingest_digest_counts); (0, n) without gpu_digest."""
+        d, c = ctypes.c_uint64(), ctypes.c_uint64()
+        L = N.lib()
+        N.check(L.fc2_ingest_digest_counts(L.fc2_caller_ingest(self.h), ctypes.byref(d), ctypes.byref(c)))
+        return int(d.value), int(c.value)
 
     def reads_gz_counts(self):
         """(pieces of spliced_reads.fastq.gz the GPU compressed, pieces its device mode left to the CPU);

@@ -135,6 +135,49 @@ int fc2_ingest_set_gpu_walk(fc2_ingest *h, int on);
 /* Blocks of the batches the GPU inflated whose record lists came from the device, and those walked on the
  * host (the blocks the device refused, or every block with the device lists off). */
 int fc2_ingest_walk_counts(const fc2_ingest *h, uint64_t *device_blocks, uint64_t *cpu_blocks);
+
+/* The record digest: the fields the ingest's BAM parser derives from a record's CIGAR, aux tags and first
+ * QUAL byte, computed on the GPU (fc2_inflate.hip bam_digest_kernel) for the record starts the walk
+ * listed, one row per listed start.  The fixed fields (flag, tid, pos, l_read_name, l_seq) are not here:
+ * the host reads them from the record's first cache line, which it touches for the query name anyway.
+ * A row with state 0 holds block_size (0 if its four bytes are not all in the byte range) and zeros. */
+typedef struct fc2_bam_digest {
+    uint8_t  state;      /* 1: the fields below are the host parser's; 0: the host parses this record */
+    uint8_t  as_type;    /* 0: no AS tag; else its BAM type char (c C s S i I f A Z H B) */
+    uint8_t  xs_type;    /* the same for XS */
+    uint8_t  has_qual;   /* !(l_seq == 0 || qual[0] == 0xFF) */
+    uint32_t block_size; /* the record's own block_size, for the host to match against the bytes it reads */
+    int32_t  astart;     /* leading clips up to the first M (aligned_start_from_cigar) */
+    int32_t  qlen;       /* len(query) with Python's slice semantics (-1 when l_seq == 0) */
+    uint32_t as_bits;    /* the value's bytes, zero- or sign-extended as its type says; 0 for A Z H B */
+    uint32_t xs_bits;
+    int64_t  aend;       /* -1 if flag & 4 or n_cigar == 0, else pos + ref_span */
+} fc2_bam_digest;
+/* Blocks of one launch at most (the ingest's largest batch). */
+#define FC2_BAM_DIGEST_MAX_BLOCKS 1024
+/* n_blocks blocks of one contiguous stream of n_bytes at `bytes` (device memory, any alignment): block i
+ * is isize[i] bytes at bytes + ooff[i], ooff ascending; starts / count are fc2_bam_walk_launch's rows
+ * (offsets into each block).  first[i] = the sum of min(count[j], FC2_BAM_WALK_CAP) over j < i, first[n_blocks]
+ * the number of rows; rows[first[i] + k] digests the record at ooff[i] + starts[i * FC2_BAM_WALK_CAP + k],
+ * which may run on into the following blocks.  State 0 (the host parses the record as ever, and raises
+ * what it raises): the record's 4 + block_size bytes are not all below n_bytes; it touches a block whose
+ * status is not 0 (status NULL: none); block_size < 32 or >= 2^28; its fields exceed the block, its name
+ * is empty or not NUL-terminated; its aux data is corrupt or ends inside a tag; AS or XS occurs more than
+ * once; a CIGAR sum (reference span, aligned start, leading or trailing soft clips) is 2^31 or more.
+ * Nothing outside [bytes, bytes + n_bytes) is read whatever the bytes say, and nothing but first[0 ..
+ * n_blocks] and rows[0 .. first[n_blocks]) written.  More than FC2_BAM_DIGEST_MAX_BLOCKS blocks: FC2_E_PARAM. */
+int fc2_bam_digest_launch(const uint8_t *bytes, uint32_t n_bytes, const uint32_t *ooff, const uint32_t *isize,
+                          const uint32_t *status, const uint16_t *starts, const uint32_t *count,
+                          fc2_bam_digest *rows, uint32_t *first, uint32_t n_blocks, void *stream);
+/* The same row for the record start at byte `at` of n_bytes bytes in host memory, from the ingest's own
+ * parser (the tests' oracle; it knows no block status).  at > n_bytes: FC2_E_RANGE. */
+int fc2_bam_digest_host(const uint8_t *bytes, uint32_t n_bytes, uint32_t at, fc2_bam_digest *row);
+/* Whether the parse threads take those fields from device rows for the records of the blocks the GPU
+ * inflated and listed (on != 0) or parse every record themselves (0, the default).  Needs the device
+ * lists (fc2_ingest_set_gpu_walk); holds from the next batch on. */
+int fc2_ingest_set_gpu_digest(fc2_ingest *h, int on);
+/* Records of the batches the GPU inflated whose fields came from device rows, and those the host parsed. */
+int fc2_ingest_digest_counts(const fc2_ingest *h, uint64_t *device_records, uint64_t *host_records);
 #ifdef __cplusplus
 }
 #endif

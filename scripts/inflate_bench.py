@@ -3,7 +3,10 @@ scripts/gen_reads' BAM (fc2_sam_to_bam, zlib level 1) inflated by fc2_bgzf_infla
 of --batch blocks (the ingest's batch) and in one launch of all, timed with HIP events on the launch
 stream, each block's CRC-32 checked on the device (and again here); the CPU leg is zlib on one core over the same blocks.
 The walk leg times fc2_bam_walk_launch (the blocks' BAM record starts) over the same blocks, in the same
-launches, from the slots the inflate left, its lists checked against fc2_bam_walk_host.  One JSON line.
+launches, from the slots the inflate left, its lists checked against fc2_bam_walk_host.  The digest leg
+times fc2_bam_digest_launch (the listed records' derived fields) over the blocks' contiguous bytes and the
+walk's lists, in launches of --batch blocks and of 1024 (its most), every 97th block's rows checked against
+fc2_bam_digest_host.  One JSON line.
 Measurement infrastructure (not part of the product).
 
 usage: python scripts/inflate_bench.py [--reads N] [--batch B] [--reps R]
@@ -107,6 +110,49 @@ def main():
         N.check(L.fc2_bam_walk_host(blk.ctypes.data, int(isz[i]), row.ctypes.data, ctypes.byref(hc), ctypes.byref(he)))
         walk_bad += not (hc.value == wc[i] and he.value == we[i] and (row[:hc.value] == ws[i, :hc.value]).all())
     wms_all, wms_batch = timed(n, walk), timed(a.batch, walk)
+    # the digest over the contiguous bytes (as the ingest's compaction leaves them) and the walk's lists:
+    # a launch sees its own blocks' bytes only, its rows dense behind those of the launches before it
+    ooff = np.concatenate([[0], np.cumsum(isz, dtype=np.int64)])
+    cont = np.concatenate([out[i * 65536:i * 65536 + isz[i]] for i in range(n)])
+    d_cont = torch.tensor(cont, device=dev)
+    rbase = np.concatenate([[0], np.cumsum(np.minimum(wc, cap), dtype=np.int64)])
+    d_rows = torch.empty(int(rbase[n]) * 32 + 32, dtype=torch.uint8, device=dev)
+    d_first = torch.empty(2 * n + 2, dtype=torch.int32, device=dev)
+    rel = {}
+
+    def digest_step(step):
+        if step not in rel:                    # block offsets relative to their launch's first block
+            r = np.concatenate([ooff[i0:min(n, i0 + step)] - ooff[i0] for i0 in range(0, n, step)])
+            rel[step] = torch.tensor(r.astype(np.uint32).view(np.int32), device=dev)
+
+        def digest(i0, i1):
+            N.check(L.fc2_bam_digest_launch(d_cont.data_ptr() + int(ooff[i0]), int(ooff[i1] - ooff[i0]),
+                                            rel[step][i0:].data_ptr(), t_isz[i0:].data_ptr(), st[i0:].data_ptr(),
+                                            w_starts[i0 * cap:].data_ptr(), w_count[i0:].data_ptr(),
+                                            d_rows.data_ptr() + int(rbase[i0]) * 32,
+                                            d_first.data_ptr() + 4 * (i0 + i0 // step), i1 - i0,
+                                            ctypes.c_void_p(stream.cuda_stream)))
+        return digest
+
+    step = min(a.batch, N.BAM_DIGEST_MAX_BLOCKS)
+    dms_batch = timed(step, digest_step(step))
+    rows = d_rows.cpu().numpy()[:int(rbase[n]) * 32].view(
+        np.dtype([("state", "u1"), ("as_type", "u1"), ("xs_type", "u1"), ("has_qual", "u1"), ("block_size", "<u4"),
+                  ("astart", "<i4"), ("qlen", "<i4"), ("as_bits", "<u4"), ("xs_bits", "<u4"), ("aend", "<i8")]))
+    first = d_first.cpu().numpy().view(np.uint32)
+    hrow, digest_bad, digest_checked = N.BamDigest(), 0, 0
+    for i in range(0, n, 97):
+        i0 = i // step * step
+        i1 = min(n, i0 + step)
+        chunk = cont[ooff[i0]:ooff[i1]]
+        f = int(first[i0 + i0 // step + (i - i0)])
+        for k in range(min(int(wc[i]), cap)):
+            N.check(L.fc2_bam_digest_host(chunk.ctypes.data, len(chunk), int(ooff[i] - ooff[i0]) + int(ws[i, k]), ctypes.byref(hrow)))
+            got = tuple(int(x) for x in rows[int(rbase[i0]) + f + k].item())
+            digest_bad += got != tuple(getattr(hrow, fld) for fld, _ in N.BamDigest._fields_)
+            digest_checked += 1
+    digest_state1 = int(rows["state"].sum())
+    dms_1024 = timed(N.BAM_DIGEST_MAX_BLOCKS, digest_step(N.BAM_DIGEST_MAX_BLOCKS))
     total = int(isz.sum())
     # CPU: zlib on one core, about 2 s of it
     t0, done, k = time.time(), 0, 0
@@ -125,7 +171,11 @@ def main():
         "walk_one_launch_ms": round(wms_all, 3), "walk_batched_ms": round(wms_batch, 3),
         "walk_share_of_inflate_one_launch": round(wms_all / ms_all, 4),
         "walk_share_of_inflate_batched": round(wms_batch / ms_batch, 4),
-        "walk_list_bytes_per_block": cap * 2 + 8}))
+        "walk_list_bytes_per_block": cap * 2 + 8,
+        "digest_rows": int(rbase[n]), "digest_rows_state1": digest_state1, "digest_rows_checked": digest_checked,
+        "digest_bad_rows": int(digest_bad), "digest_batch": step, "digest_batched_ms": round(dms_batch, 3),
+        "digest_1024_ms": round(dms_1024, 3), "digest_share_of_inflate_batched": round(dms_batch / ms_batch, 4),
+        "digest_row_bytes": int(rbase[n]) * 32, "digest_row_bytes_share_of_inflated": round(int(rbase[n]) * 32 / total, 4)}))
 
 
 if __name__ == "__main__":
