@@ -7,6 +7,7 @@ fallback: if the library is missing, importing a GPU entry point raises.
 from __future__ import annotations
 
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -214,14 +215,10 @@ _lib = None
 
 def build(force: bool = False) -> str:
     srcdir = os.path.join(_HERE, "csrc")
-    srcs = [os.path.join(srcdir, f) for f in ("fc2_kernels.hip", "fc2_scan32.hip", "fc2_reorder.hip", "fc2_inflate.hip",
-                                              "fc2_deflate.hip", "fc2_deflate_gpu.hip", "fc2_deflate_gpu.h", "fc2_devcrc.h",
-                                              "fc2_gzpieces.h", "fc2_scan32.h",
-                                              "fc2_host.cpp", "fc2_ingest.cpp", "fc2_ingest_impl.h", "fc2_caller.cpp",
-                                              "fc2_bamout.cpp", "fc2_bamout.h", "fc2_ctx.cpp", "fc2_hostmem.h",
-                                              "fc2_common.h", "Makefile")]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h)
-             for h in ("fc2_bp.h", "fc2_ingest.h", "fc2_caller.h", "fc2_ctx.h")]
+    # every source and header of the library, and the Makefile (whose HDRS are the same wildcards)
+    srcs = [os.path.join(srcdir, "Makefile")] + glob.glob(os.path.join(os.path.dirname(_HERE), "include", "*.h"))
+    for pat in ("*.hip", "*.cpp", "*.h"):
+        srcs += glob.glob(os.path.join(srcdir, pat))
     newest = max(os.path.getmtime(s) for s in srcs)
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
         subprocess.check_call(["make", "-s", "-C", srcdir])

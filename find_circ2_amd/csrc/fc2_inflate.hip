@@ -16,8 +16,8 @@
 // two waves a SIMD, one decoding while the other waits.  A table entry carries the symbol's
 // meaning (literal / length or distance base and its extra-bit count / end of block), so a length
 // or a distance is one lookup and one shift.  Every access is bounds-checked: a malformed block sets
-// its status word, and the host, which checks each block's CRC-32 and ISIZE on the bytes it copies
-// back, inflates any block the GPU refused on the CPU.
+// its status word, as does one whose CRC-32 or ISIZE the device finds wrong; the host inflates any
+// block the GPU refused on the CPU, and checks CRC-32 and ISIZE only on the blocks it inflates itself.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -853,16 +853,40 @@ bool pinned_give(void *b) {
 // for this kernel (eight 20 KB workgroups a CU), so the breakpoint search's kernels find room
 constexpr int kStreams = 4;
 
+// the blocks' table by column, M entries each in one allocation: the payload's offset in the input
+// and its length, ISIZE, CRC-32, the output offset in the batch, the device's status, and the output
+// offset in the block's chunk (the digest kernel's)
+struct Cols {
+    uint32_t *off, *len, *isize, *crc, *ooff, *status, *rooff;
+    static constexpr size_t kCount = 7;
+    static Cols of(uint32_t *b, size_t M) { return {b, b + M, b + 2 * M, b + 3 * M, b + 4 * M, b + 5 * M, b + 6 * M}; }
+};
+struct WalkCols {                              // a block's listed record starts: how many, and the walk's exit
+    uint32_t *count, *exit;
+    static constexpr size_t kCount = 2;
+    static WalkCols of(uint32_t *b, size_t M) { return {b, b + M}; }
+};
+// blocks [i0, i0 + c) of the batch under way: input bytes [b0, b1), output bytes [o0, o1), on stream s;
+// a digested chunk's first[] lies at foff of d_first / h_first, its first row at row0 of h_rows
+struct Chunk {
+    uint32_t i0, c;
+    size_t b0, b1;
+    uint64_t o0, o1, row0;
+    uint32_t foff;
+    int s;
+};
+
 struct Gpu {
     int device = 0;
     uint32_t max_blocks = 0;
     size_t src_cap = 0;
     hipStream_t stream[kStreams] = {};
     hipEvent_t done[kStreams] = {};            // blocking-sync: the reader thread sleeps, not spins
+    std::vector<std::pair<void *, bool>> bufs; // every buffer below and whether it is pinned (make): gpu_close frees them
     uint8_t *h_src = nullptr, *d_src = nullptr, *d_slots = nullptr, *d_out = nullptr;
-    uint32_t *h_meta = nullptr, *d_meta = nullptr;      // off | len | isize | crc | ooff | status | ooff in the chunk
+    Cols h{}, d{};                             // the blocks' table, pinned and on the device
     // the blocks' record lists (bam_walk_kernel): count | exit, and a row of starts per block
-    uint32_t *h_walk = nullptr, *d_walk = nullptr;
+    WalkCols h_walk{}, d_walk{};
     uint16_t *h_starts = nullptr, *d_starts = nullptr;
     bool walk = false;                         // this batch's blocks are listed on the device
     // the listed records' digest rows (bam_digest_kernel), made by the first batch that asks for them:
@@ -871,28 +895,38 @@ struct Gpu {
     fc2_bam_digest *d_rows = nullptr, *h_rows = nullptr;
     uint32_t *d_first = nullptr, *h_first = nullptr;
     size_t rows_cap = 0;                       // rows h_rows holds (a batch with more gets no digests)
-    struct Chunk {
-        uint32_t i0, c, foff;
-        int s;
-        uint64_t row0;                         // its first row in h_rows
-    };
-    std::vector<Chunk> dchunks;
-    bool digest = false, digest_ok = false, rows_ready = false;
+    std::vector<Chunk> dchunks;                // the chunks that were digested
+    bool digest = false, rows_ready = false;
     bool pooled = false;
     // the batch under way (gpu_begin .. gpu_finish)
     char *dest = nullptr;
     uint32_t n = 0;                            // blocks submitted
-    uint64_t out = 0;                          // their inflated bytes
-    int chunks = 0;
+    int chunks = 0;                            // chunks given to the device
+    bool spilled = false;                      // a block over 64 KiB was met: the CPU's from there on, no digests
     bool ok = true;
     std::string err;
 };
 
-static bool hip_ok(Gpu *g, hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    if (g->ok) g->err = std::string("GPU inflate: ") + what + ": " + hipGetErrorString(e);
+static bool fail(Gpu *g, const std::string &what) {      // the first failure is the batch's error
+    if (g->ok) g->err = "GPU inflate: " + what;
     g->ok = false;
     return false;
+}
+static bool hip_ok(Gpu *g, hipError_t e, const char *what) {
+    return e == hipSuccess || fail(g, std::string(what) + ": " + hipGetErrorString(e));
+}
+static bool copy(Gpu *g, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    return hip_ok(g, hipMemcpyAsync(dst, src, bytes, kind, s), kind == hipMemcpyHostToDevice ? "upload" : "download");
+}
+// a device buffer, or a pinned host one, of n elements: listed in g->bufs, which gpu_close frees
+template <class T>
+static bool make(Gpu *g, T *&p, size_t n, bool pinned, const char *what) {
+    void *v = nullptr;
+    if (!hip_ok(g, pinned ? hipHostMalloc(&v, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&v, n * sizeof(T)), what))
+        return false;
+    g->bufs.push_back({v, pinned});
+    p = static_cast<T *>(v);
+    return true;
 }
 
 Gpu *gpu_open(int device, uint32_t max_blocks, size_t pool_cap, std::string &err) {
@@ -900,27 +934,26 @@ Gpu *gpu_open(int device, uint32_t max_blocks, size_t pool_cap, std::string &err
     g->device = device;
     g->max_blocks = max_blocks;
     g->src_cap = (size_t)max_blocks * kOutMax + 64;      // a BGZF block is at most 64 KiB
-    const size_t out = (size_t)max_blocks * kOutMax, meta = (size_t)max_blocks * 7 * sizeof(uint32_t);
-    const size_t walk = (size_t)max_blocks * 2 * sizeof(uint32_t), rows = (size_t)max_blocks * kWalkCap * sizeof(uint16_t);
+    const size_t M = max_blocks, out = M * kOutMax;
+    uint32_t *h_meta = nullptr, *d_meta = nullptr, *h_walk = nullptr, *d_walk = nullptr;
     bool ok = hip_ok(g, hipSetDevice(device), "hipSetDevice");
     for (int k = 0; k < kStreams && ok; ++k)
         ok = hip_ok(g, hipStreamCreateWithFlags(&g->stream[k], hipStreamNonBlocking), "stream") &&
              hip_ok(g, hipEventCreateWithFlags(&g->done[k], hipEventBlockingSync | hipEventDisableTiming), "event");
-    ok = ok && hip_ok(g, hipHostMalloc((void **)&g->h_src, g->src_cap, hipHostMallocDefault), "pinned input") &&
-         hip_ok(g, hipHostMalloc((void **)&g->h_meta, meta, hipHostMallocDefault), "pinned table") &&
-         hip_ok(g, hipMalloc((void **)&g->d_src, g->src_cap), "device input") &&
-         hip_ok(g, hipMalloc((void **)&g->d_slots, out), "device slots") &&
-         hip_ok(g, hipMalloc((void **)&g->d_out, out), "device output") &&
-         hip_ok(g, hipMalloc((void **)&g->d_meta, meta), "device table") &&
-         hip_ok(g, hipHostMalloc((void **)&g->h_walk, walk, hipHostMallocDefault), "pinned record counts") &&
-         hip_ok(g, hipHostMalloc((void **)&g->h_starts, rows, hipHostMallocDefault), "pinned record lists") &&
-         hip_ok(g, hipMalloc((void **)&g->d_walk, walk), "device record counts") &&
-         hip_ok(g, hipMalloc((void **)&g->d_starts, rows), "device record lists");
+    ok = ok && make(g, g->h_src, g->src_cap, true, "pinned input") && make(g, h_meta, M * Cols::kCount, true, "pinned table") &&
+         make(g, g->d_src, g->src_cap, false, "device input") && make(g, g->d_slots, out, false, "device slots") &&
+         make(g, g->d_out, out, false, "device output") && make(g, d_meta, M * Cols::kCount, false, "device table") &&
+         make(g, h_walk, M * WalkCols::kCount, true, "pinned record counts") &&
+         make(g, g->h_starts, M * kWalkCap, true, "pinned record lists") &&
+         make(g, d_walk, M * WalkCols::kCount, false, "device record counts") &&
+         make(g, g->d_starts, M * kWalkCap, false, "device record lists");
     if (!ok) {
         err = g->err;
         gpu_close(g);
         return nullptr;
     }
+    g->h = Cols::of(h_meta, M), g->d = Cols::of(d_meta, M);
+    g->h_walk = WalkCols::of(h_walk, M), g->d_walk = WalkCols::of(d_walk, M);
     if (pool_cap) {              // the batches the parse blocks and the read loop's chunks still hold, and one in flight
         pool_open(pool_cap, 16);
         g->pooled = true;
@@ -937,20 +970,7 @@ void gpu_close(Gpu *g) {
     if (hipSetDevice(g->device) == hipSuccess) {
         for (int k = 0; k < kStreams; ++k)
             if (g->stream[k]) (void)hipStreamSynchronize(g->stream[k]);
-        if (g->d_first) (void)hipFree(g->d_first);
-        if (g->d_rows) (void)hipFree(g->d_rows);
-        if (g->h_first) (void)hipHostFree(g->h_first);
-        if (g->h_rows) (void)hipHostFree(g->h_rows);
-        if (g->d_starts) (void)hipFree(g->d_starts);
-        if (g->d_walk) (void)hipFree(g->d_walk);
-        if (g->h_starts) (void)hipHostFree(g->h_starts);
-        if (g->h_walk) (void)hipHostFree(g->h_walk);
-        if (g->d_meta) (void)hipFree(g->d_meta);
-        if (g->d_out) (void)hipFree(g->d_out);
-        if (g->d_slots) (void)hipFree(g->d_slots);
-        if (g->d_src) (void)hipFree(g->d_src);
-        if (g->h_meta) (void)hipHostFree(g->h_meta);
-        if (g->h_src) (void)hipHostFree(g->h_src);
+        for (auto b = g->bufs.rbegin(); b != g->bufs.rend(); ++b) (void)(b->second ? hipHostFree(b->first) : hipFree(b->first));
         for (int k = 0; k < kStreams; ++k) {
             if (g->done[k]) (void)hipEventDestroy(g->done[k]);
             if (g->stream[k]) (void)hipStreamDestroy(g->stream[k]);
@@ -969,113 +989,106 @@ void gpu_begin(Gpu *g, char *dest, bool walk, bool digest) {
     g->dest = dest;
     g->walk = walk;
     g->digest = walk && digest;
-    g->digest_ok = g->digest;
-    g->rows_ready = false;
+    g->spilled = g->rows_ready = false;
     g->dchunks.clear();
     g->n = 0;
-    g->out = 0;
     g->chunks = 0;
     g->ok = hipSetDevice(g->device) == hipSuccess;
     g->err = g->ok ? "" : "GPU inflate: hipSetDevice failed";
     if (g->ok && g->digest && !g->d_rows) {
         const size_t M = g->max_blocks;
         g->rows_cap = M * kRowsPerBlock;
-        hip_ok(g, hipMalloc((void **)&g->d_rows, M * kWalkCap * sizeof(fc2_bam_digest)), "device digest rows") &&
-            hip_ok(g, hipMalloc((void **)&g->d_first, (2 * M + 1) * sizeof(uint32_t)), "device row index") &&
-            hip_ok(g, hipHostMalloc((void **)&g->h_rows, g->rows_cap * sizeof(fc2_bam_digest), hipHostMallocDefault),
-                   "pinned digest rows") &&
-            hip_ok(g, hipHostMalloc((void **)&g->h_first, (2 * M + 1) * sizeof(uint32_t), hipHostMallocDefault),
-                   "pinned row index");
+        make(g, g->d_rows, M * kWalkCap, false, "device digest rows") && make(g, g->d_first, 2 * M + 1, false, "device row index") &&
+            make(g, g->h_rows, g->rows_cap, true, "pinned digest rows") && make(g, g->h_first, 2 * M + 1, true, "pinned row index");
     }
 }
 
-bool gpu_add(Gpu *g, const uint8_t *raw, const size_t *boff, const size_t *bsz, size_t i0, size_t i1) {
+constexpr size_t kWord = sizeof(uint32_t);
+
+// Stage 1: the chunk's columns into the pinned table and its bytes into the pinned input (at their
+// offsets in the batch, 8 zero bytes behind).  false: the chunk holds a block over 64 KiB, or follows
+// one -- not BGZF, and its bytes may lie past what the buffers hold: the CPU inflates (and reports) its
+// blocks and those of every later chunk; the chunks before it hold in-spec sizes only
+static bool stage_chunk(Gpu *g, const uint8_t *raw, const Block *blocks, const Chunk &ch) {
+    const Cols &h = g->h;
+    for (size_t i = ch.i0; i < ch.i0 + ch.c; ++i) {
+        const Block &b = blocks[i];
+        g->spilled = g->spilled || b.isize > kOutMax || b.out + b.isize > (uint64_t)g->max_blocks * kOutMax;
+        h.off[i] = (uint32_t)b.payload, h.len[i] = (uint32_t)b.len, h.isize[i] = b.isize, h.crc[i] = b.crc;
+        h.ooff[i] = (uint32_t)b.out, h.rooff[i] = (uint32_t)(b.out - ch.o0);
+    }
+    if (g->spilled) {
+        std::fill(h.status + ch.i0, h.status + ch.i0 + ch.c, (uint32_t)INF_TOO_BIG);
+        return false;
+    }
+    memcpy(g->h_src + ch.b0, raw + ch.b0, ch.b1 - ch.b0);
+    memset(g->h_src + ch.b1, 0, 8);
+    return true;
+}
+
+// Stage 2: the bytes and the five columns the inflate and the compaction read go up; each block is
+// inflated into its slot, then moved to its place in the batch
+static bool enqueue_inflate(Gpu *g, const Chunk &ch) {
+    hipStream_t s = g->stream[ch.s];
+    const size_t i0 = ch.i0;
+    const Cols &h = g->h, &d = g->d;
+    bool ok = copy(g, g->d_src + ch.b0, g->h_src + ch.b0, ch.b1 + 8 - ch.b0, hipMemcpyHostToDevice, s);
+    for (uint32_t *Cols::*col : {&Cols::off, &Cols::len, &Cols::isize, &Cols::crc, &Cols::ooff})
+        ok = ok && copy(g, d.*col + i0, h.*col + i0, ch.c * kWord, hipMemcpyHostToDevice, s);
+    if (!ok || fc2_bgzf_inflate_launch(g->d_src, d.off + i0, d.len + i0, d.isize + i0, d.crc + i0, g->d_slots + i0 * kOutMax,
+                                       d.status + i0, ch.c, s) != FC2_OK)
+        return fail(g, "launch failed");
+    hipLaunchKernelGGL(compact_kernel, dim3(kOutMax / 16 / 256, ch.c), dim3(256), 0, s, g->d_slots + i0 * kOutMax,
+                       d.isize + i0, d.ooff + i0, d.status + i0, g->d_out);
+    return hip_ok(g, hipGetLastError(), "compact");
+}
+// Stage 3: the blocks' record lists, from the slots the compaction leaves as they are, and their download
+static bool enqueue_walk(Gpu *g, const Chunk &ch) {
+    hipStream_t s = g->stream[ch.s];
+    const size_t i0 = ch.i0, r0 = i0 * kWalkCap;
+    const WalkCols &h = g->h_walk, &d = g->d_walk;
+    if (fc2_bam_walk_launch(g->d_slots + i0 * kOutMax, g->d.isize + i0, g->d.status + i0, g->d_starts + r0, d.count + i0,
+                            d.exit + i0, ch.c, s) != FC2_OK)
+        return fail(g, "record list launch failed");
+    return copy(g, g->h_starts + r0, g->d_starts + r0, (size_t)ch.c * kWalkCap * sizeof(uint16_t), hipMemcpyDeviceToHost, s) &&
+           copy(g, h.count + i0, d.count + i0, ch.c * kWord, hipMemcpyDeviceToHost, s) &&
+           copy(g, h.exit + i0, d.exit + i0, ch.c * kWord, hipMemcpyDeviceToHost, s);
+}
+
+// Stage 4: the listed records' digest rows, from the chunk's contiguous bytes (records cross blocks),
+// and the download of its row index; the rows follow in gpu_finish
+static bool enqueue_digest(Gpu *g, Chunk ch) {
+    hipStream_t s = g->stream[ch.s];
+    const size_t i0 = ch.i0, r0 = i0 * kWalkCap;
+    ch.foff = (uint32_t)(i0 + g->dchunks.size());
+    if (!copy(g, g->d.rooff + i0, g->h.rooff + i0, ch.c * kWord, hipMemcpyHostToDevice, s)) return false;
+    if (fc2_bam_digest_launch(g->d_out + ch.o0, (uint32_t)(ch.o1 - ch.o0), g->d.rooff + i0, g->d.isize + i0, g->d.status + i0,
+                              g->d_starts + r0, g->d_walk.count + i0, g->d_rows + r0, g->d_first + ch.foff, ch.c, s) != FC2_OK)
+        return fail(g, "record digest launch failed");
+    if (!copy(g, g->h_first + ch.foff, g->d_first + ch.foff, (ch.c + 1) * kWord, hipMemcpyDeviceToHost, s)) return false;
+    g->dchunks.push_back(ch);
+    return true;
+}
+
+// Stage 5: the chunk's bytes into the batch buffer, and its statuses
+static bool enqueue_download(Gpu *g, const Chunk &ch) {
+    hipStream_t s = g->stream[ch.s];
+    return copy(g, g->dest + ch.o0, g->d_out + ch.o0, ch.o1 - ch.o0, hipMemcpyDeviceToHost, s) &&
+           copy(g, g->h.status + ch.i0, g->d.status + ch.i0, ch.c * kWord, hipMemcpyDeviceToHost, s);
+}
+
+bool gpu_add(Gpu *g, const uint8_t *raw, const Block *blocks, size_t i0, size_t i1) {
     if (!g->ok) return false;
     if (i1 <= i0) return true;
-    if (i0 != g->n || i1 > g->max_blocks || boff[i1 - 1] + bsz[i1 - 1] + 8 > g->src_cap) {
-        g->ok = false;
-        g->err = "GPU inflate: chunk out of order or larger than the buffers";
-        return false;
-    }
-    const uint32_t M = g->max_blocks;
-    uint32_t *off = g->h_meta, *len = off + M, *isz = len + M, *crc = isz + M, *ooff = crc + M, *st = ooff + M,
-             *rooff = st + M;
-    // the chunk's bytes into the pinned input (at their offsets in the batch), 8 zero bytes behind
-    const size_t b0 = boff[i0], b1 = boff[i1 - 1] + bsz[i1 - 1];
-    memcpy(g->h_src + b0, raw + b0, b1 - b0);
-    memset(g->h_src + b1, 0, 8);
-    bool fits = true;
-    for (size_t i = i0; i < i1; ++i) {
-        const uint8_t *b = raw + boff[i];
-        const size_t xl = b[10] | (b[11] << 8);
-        off[i] = (uint32_t)(boff[i] + 12 + xl);
-        len[i] = (uint32_t)(bsz[i] - 12 - xl - 8);
-        const uint8_t *t = b + bsz[i] - 8;
-        crc[i] = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
-        isz[i] = t[4] | (t[5] << 8) | (t[6] << 16) | ((uint32_t)t[7] << 24);
-        ooff[i] = (uint32_t)g->out;
-        rooff[i] = ooff[i] - ooff[i0];
-        if (isz[i] > kOutMax) fits = false;
-        g->out += std::min<uint32_t>(isz[i], kOutMax);
-    }
+    const Block &first = blocks[i0], &last = blocks[i1 - 1];
+    if (i0 != g->n || i1 > g->max_blocks || last.at + last.size + 8 > g->src_cap)
+        return fail(g, "chunk out of order or larger than the buffers");
     g->n = (uint32_t)i1;
-    const uint32_t c = (uint32_t)(i1 - i0);
-    if (!fits) {                               // not BGZF: the CPU inflates (and reports) these blocks
-        for (size_t i = i0; i < i1; ++i) st[i] = INF_TOO_BIG;
-        g->digest_ok = false;                  // (the host's offsets differ from the device's from here on)
-        return true;
-    }
-    hipStream_t s = g->stream[g->chunks++ % kStreams];
-    uint32_t *d_off = g->d_meta, *d_len = d_off + M, *d_isz = d_len + M, *d_crc = d_isz + M, *d_ooff = d_crc + M,
-             *d_st = d_ooff + M;
-    const size_t w = sizeof(uint32_t);
-    bool ok = hip_ok(g, hipMemcpyAsync(g->d_src + b0, g->h_src + b0, b1 + 8 - b0, hipMemcpyHostToDevice, s), "upload");
-    for (int a = 0; a < 5 && ok; ++a)
-        ok = hip_ok(g, hipMemcpyAsync(g->d_meta + (size_t)a * M + i0, g->h_meta + (size_t)a * M + i0, c * w,
-                                      hipMemcpyHostToDevice, s), "upload");
-    ok = ok && fc2_bgzf_inflate_launch(g->d_src, d_off + i0, d_len + i0, d_isz + i0, d_crc + i0,
-                                       g->d_slots + (size_t)i0 * kOutMax, d_st + i0, c, s) == FC2_OK;
-    if (!ok) {
-        if (g->ok) g->err = "GPU inflate: launch failed";
-        g->ok = false;
-        return false;
-    }
-    hipLaunchKernelGGL(compact_kernel, dim3(kOutMax / 16 / 256, c), dim3(256), 0, s, g->d_slots + (size_t)i0 * kOutMax,
-                       d_isz + i0, d_ooff + i0, d_st + i0, g->d_out);
-    const uint64_t o0 = ooff[i0];
-    if (!hip_ok(g, hipGetLastError(), "compact")) return false;
-    if (g->walk) {                             // the blocks' record lists, from the slots the compaction leaves as they are
-        if (fc2_bam_walk_launch(g->d_slots + (size_t)i0 * kOutMax, d_isz + i0, d_st + i0, g->d_starts + (size_t)i0 * kWalkCap,
-                                g->d_walk + i0, g->d_walk + M + i0, c, s) != FC2_OK) {
-            if (g->ok) g->err = "GPU inflate: record list launch failed";
-            g->ok = false;
-            return false;
-        }
-        ok = hip_ok(g, hipMemcpyAsync(g->h_starts + (size_t)i0 * kWalkCap, g->d_starts + (size_t)i0 * kWalkCap,
-                                      (size_t)c * kWalkCap * sizeof(uint16_t), hipMemcpyDeviceToHost, s), "download") &&
-             hip_ok(g, hipMemcpyAsync(g->h_walk + i0, g->d_walk + i0, c * w, hipMemcpyDeviceToHost, s), "download") &&
-             hip_ok(g, hipMemcpyAsync(g->h_walk + M + i0, g->d_walk + M + i0, c * w, hipMemcpyDeviceToHost, s), "download");
-        if (!ok) return false;
-    }
-    if (g->digest && g->digest_ok && c <= kDigestMaxBlocks) {
-        // the listed records' digest rows, from the chunk's contiguous bytes (records cross blocks)
-        Gpu::Chunk ch{(uint32_t)i0, c, (uint32_t)(i0 + g->dchunks.size()), (int)((g->chunks - 1) % kStreams), 0};
-        uint32_t *d_rooff = d_st + M;
-        ok = hip_ok(g, hipMemcpyAsync(d_rooff + i0, rooff + i0, c * w, hipMemcpyHostToDevice, s), "upload");
-        if (ok && fc2_bam_digest_launch(g->d_out + o0, (uint32_t)(g->out - o0), d_rooff + i0, d_isz + i0, d_st + i0,
-                                        g->d_starts + (size_t)i0 * kWalkCap, g->d_walk + i0,
-                                        g->d_rows + (size_t)i0 * kWalkCap, g->d_first + ch.foff, c, s) != FC2_OK) {
-            if (g->ok) g->err = "GPU inflate: record digest launch failed";
-            g->ok = false;
-            return false;
-        }
-        ok = ok && hip_ok(g, hipMemcpyAsync(g->h_first + ch.foff, g->d_first + ch.foff, (c + 1) * w, hipMemcpyDeviceToHost, s),
-                          "download");
-        if (!ok) return false;
-        g->dchunks.push_back(ch);
-    }
-    return hip_ok(g, hipMemcpyAsync(g->dest + o0, g->d_out + o0, g->out - o0, hipMemcpyDeviceToHost, s), "download") &&
-           hip_ok(g, hipMemcpyAsync(st + i0, d_st + i0, c * w, hipMemcpyDeviceToHost, s), "download");
+    Chunk ch{(uint32_t)i0, (uint32_t)(i1 - i0), first.at, last.at + last.size, first.out, last.out + last.isize, 0, 0, 0};
+    if (!stage_chunk(g, raw, blocks, ch)) return true;
+    ch.s = g->chunks++ % kStreams;
+    return enqueue_inflate(g, ch) && (!g->walk || enqueue_walk(g, ch)) &&
+           (!g->digest || ch.c > kDigestMaxBlocks || enqueue_digest(g, ch)) && enqueue_download(g, ch);
 }
 
 bool gpu_finish(Gpu *g, std::string &err) {
@@ -1083,18 +1096,18 @@ bool gpu_finish(Gpu *g, std::string &err) {
         if (hip_ok(g, hipEventRecord(g->done[k], g->stream[k]), "event")) hip_ok(g, hipEventSynchronize(g->done[k]), "kernel");
     // the digest rows, now that every chunk's first[] says how many there are: a sized download per
     // chunk on its stream, side by side, then the same wait again
-    if (g->ok && g->digest && g->digest_ok && !g->dchunks.empty()) {
+    if (g->ok && g->digest && !g->spilled && !g->dchunks.empty()) {
         uint64_t total = 0;
-        for (Gpu::Chunk &ch : g->dchunks) {
+        for (Chunk &ch : g->dchunks) {
             ch.row0 = total;
             total += std::min<uint64_t>(g->h_first[ch.foff + ch.c], (uint64_t)ch.c * kWalkCap);
         }
         if (total <= g->rows_cap) {
             bool used[kStreams] = {};
-            for (const Gpu::Chunk &ch : g->dchunks) {
+            for (const Chunk &ch : g->dchunks) {
                 const uint64_t n = std::min<uint64_t>(g->h_first[ch.foff + ch.c], (uint64_t)ch.c * kWalkCap);
-                if (n && hip_ok(g, hipMemcpyAsync(g->h_rows + ch.row0, g->d_rows + (size_t)ch.i0 * kWalkCap,
-                                                  n * sizeof(fc2_bam_digest), hipMemcpyDeviceToHost, g->stream[ch.s]), "download"))
+                if (n && copy(g, g->h_rows + ch.row0, g->d_rows + (size_t)ch.i0 * kWalkCap, n * sizeof(fc2_bam_digest),
+                              hipMemcpyDeviceToHost, g->stream[ch.s]))
                     used[ch.s] = true;
             }
             for (int k = 0; k < kStreams; ++k)
@@ -1107,18 +1120,18 @@ bool gpu_finish(Gpu *g, std::string &err) {
     return g->ok;
 }
 
-uint32_t gpu_status(const Gpu *g, size_t i) { return g->h_meta[5 * (size_t)g->max_blocks + i]; }
+uint32_t gpu_status(const Gpu *g, size_t i) { return g->h.status[i]; }
 
 const uint16_t *gpu_walk(const Gpu *g, size_t i, uint32_t &count, uint32_t &exit) {
-    count = std::min<uint32_t>(g->h_walk[i], kWalkCap);
-    exit = g->h_walk[(size_t)g->max_blocks + i];
+    count = std::min<uint32_t>(g->h_walk.count[i], kWalkCap);
+    exit = g->h_walk.exit[i];
     return g->h_starts + i * kWalkCap;
 }
 
 const fc2_bam_digest *gpu_digest(const Gpu *g, size_t i, uint32_t &count) {
     count = 0;
     if (!g->rows_ready) return nullptr;
-    for (const Gpu::Chunk &ch : g->dchunks)
+    for (const Chunk &ch : g->dchunks)
         if (i >= ch.i0 && i < ch.i0 + ch.c) {
             const uint32_t *f = g->h_first + ch.foff;
             const uint32_t a = f[i - ch.i0], b = f[i - ch.i0 + 1];

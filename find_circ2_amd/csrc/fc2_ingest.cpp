@@ -198,7 +198,7 @@ using CharBuf = std::vector<char, NoInitAlloc<char>>;
 // record cut by the previous batch's end there instead of copying the batch (bgzf_split_loop)
 constexpr size_t kHead = size_t(1) << 16;
 
-constexpr uint64_t kNoExit = ~uint64_t(0);
+constexpr uint64_t kNoExit = ~uint64_t(0), kNoRows = ~uint64_t(0);
 
 // The BAM records of one inflated batch as the inflating threads saw them (bgzf_split_loop jumps
 // through these instead of reading every record's block_size from cold memory on its one thread):
@@ -216,8 +216,30 @@ struct RecLists {
     bool gpu = false;
     std::vector<fc2_bam_digest> rows;
     std::vector<uint64_t> row0;
+
+    bool holds(size_t k, size_t q) const { return q >= ooff[k] && q < ooff[k + 1]; }
+    // the block holding batch offset q (q < n)
+    size_t block_of(size_t q) const { return (size_t)(std::upper_bound(ooff.begin(), ooff.end(), q) - ooff.begin()) - 1; }
+    // where batch offset q stands among block k's listed starts (the end: it is not one of them)
+    std::vector<uint32_t>::const_iterator listed(size_t k, size_t q) const {
+        const auto it = std::lower_bound(starts[k].begin(), starts[k].end(), (uint32_t)q);
+        return it != starts[k].end() && *it == q ? it : starts[k].end();
+    }
+    // a forward cursor (block k, its listed start m) moved to batch offset q (q < n; the offsets of a
+    // chain of records only grow): true if q is that listed start
+    bool seek(size_t &k, size_t &m, size_t q) const {
+        if (!holds(k, q)) {
+            k = k + 1 < starts.size() && holds(k + 1, q) ? k + 1 : block_of(q);
+            m = 0;
+        }
+        const std::vector<uint32_t> &S = starts[k];
+        if (m < S.size() && S[m] > q) m = 0;    // (never on a chain of growing offsets)
+        while (m < S.size() && S[m] < q) ++m;
+        return m < S.size() && S[m] == q;
+    }
+    // the digest row of block k's listed start m, of a batch that has rows (null: the block has none)
+    const fc2_bam_digest *row(size_t k, size_t m) const { return row0[k] == kNoRows ? nullptr : &rows[row0[k] + m]; }
 };
-constexpr uint64_t kNoRows = ~uint64_t(0);
 
 struct BgzfBatch {
     CharBuf out;                 // kHead bytes of headroom, then the inflated bytes
@@ -344,177 +366,187 @@ static int64_t now_ns() {
 
 constexpr size_t kGpuChunk = 256;              // blocks per GPU chunk (16 MiB inflated)
 
-// reads up to `max_blocks` blocks (the first `pre` bytes of the first header are in `pre`)
-BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_threads, std::shared_ptr<GpuInflate> gi) {
-    BgzfBatch B;
-    std::vector<uint8_t> raw;
-    std::vector<size_t> boff, bsz;
-    raw.swap(pre);
+using fc2::inf::Block;
+
+uint32_t le32(const uint8_t *p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+// whether the GPU inflates the next batch: the device is set, has not failed, and its buffers are there
+bool batch_on_device(GpuInflate *gi, int max_blocks) {
     if (gi && !gi->launched && gi->read_bytes >= gi->start_after) gi->launch(false);
-    // the GPU inflates the batch in chunks as they are read (fc2_inflate.h), into the batch buffer
-    // itself -- a pinned one from the pool, made max_blocks * 64 KiB long up front
-    bool gpu = gi && !gi->failed && max_blocks <= (int)gi->max_blocks;
+    if (!gi || gi->failed || max_blocks > (int)gi->max_blocks) return false;
     // the device's buffers and the pinned pool, made meanwhile: until they are ready (pinning the
     // buffers takes a few hundred ms) the batches are inflated on the CPU
-    if (gpu && !gi->g && gi->opening.valid() &&
-        gi->opening.wait_for(std::chrono::seconds(0)) == std::future_status::ready) {
+    if (!gi->g && gi->opening.valid() && gi->opening.wait_for(std::chrono::seconds(0)) == std::future_status::ready) {
         auto r = gi->opening.get();
         gi->g = r.first;
         if (!gi->g) gi->failed = true, gi->err = r.second;
     }
-    gpu = gpu && gi->g;
-    const bool dev_lists = gpu && gi->walk.load();
-    const bool dev_digest = dev_lists && gi->digest.load();
-    size_t submitted = 0;
+    return gi->g != nullptr;
+}
+
+// Step 1: up to max_blocks blocks read from fd into raw (which may hold the first bytes of the first
+// header) and listed in the block table -- the one place a block's header and trailer are decoded.
+// With dev, the blocks go to the GPU as they are read, in chunks of kGpuChunk (fc2_inflate.h).
+// B.err / B.eof: how the reading ended
+void read_blocks(int fd, int max_blocks, std::vector<uint8_t> &raw, std::vector<Block> &blocks, GpuInflate *dev,
+                 BgzfBatch &B) {
+    size_t pos = 0, submitted = 0;
     auto submit = [&](bool last) {             // blocks read so far, in chunks of kGpuChunk
-        if (!gpu) return;
-        if (boff.size() - submitted < kGpuChunk && !(last && boff.size() > submitted)) return;
+        if (!dev) return;
+        if (blocks.size() - submitted < kGpuChunk && !(last && blocks.size() > submitted)) return;
         fc2::cpu::Scope acct(fc2::cpu::INFLATE);
         const int64_t a0 = now_ns();
-        fc2::inf::gpu_add(gi->g, raw.data(), boff.data(), bsz.data(), submitted, boff.size());
-        gi->add_ns += now_ns() - a0;
-        submitted = boff.size();
+        fc2::inf::gpu_add(dev->g, raw.data(), blocks.data(), submitted, blocks.size());
+        dev->add_ns += now_ns() - a0;
+        submitted = blocks.size();
     };
-    const int64_t t0 = now_ns();
-    if (gpu) {
-        B.out.resize(kHead + (size_t)max_blocks * 65536);
-        fc2::inf::gpu_begin(gi->g, B.out.data() + kHead, dev_lists, dev_digest);
-        gi->batches += 1;
-        gi->pinned += fc2::inf::pinned_owns(B.out.data());
-    }
-    size_t pos = 0;
-    while ((int)boff.size() < max_blocks) {
-        size_t got;
-        if (raw.size() - pos < 18) {           // header
-            const size_t have = raw.size() - pos;
-            raw.resize(pos + 18);
-            if (!read_full(fd, raw.data() + pos + have, 18 - have, got)) { B.err = "read error"; break; }
-            if (have + got == 0) { raw.resize(pos); B.eof = true; break; }
-            if (have + got < 18) { B.err = "truncated BGZF block header"; break; }
-        }
+    bool io = true;                            // false: read(2) failed
+    auto fill = [&](size_t need) {             // the bytes raw holds of the block at pos: `need`, or what the input still had
+        const size_t have = raw.size() - pos;
+        size_t got = 0;
+        if (have >= need) return have;
+        raw.resize(pos + need);
+        io = read_full(fd, raw.data() + pos + have, need - have, got);
+        return have + got;
+    };
+    while ((int)blocks.size() < max_blocks) {
+        const size_t head = fill(18);
+        if (!io) { B.err = "read error"; break; }
+        if (head == 0) { raw.resize(pos); B.eof = true; break; }
+        if (head < 18) { B.err = "truncated BGZF block header"; break; }
         const size_t xlen = raw[pos + 10] | (raw[pos + 11] << 8);
-        if (raw.size() - pos < 12 + xlen) {
-            const size_t have = raw.size() - pos;
-            raw.resize(pos + 12 + xlen);
-            if (!read_full(fd, raw.data() + pos + have, 12 + xlen - have, got) || got < 12 + xlen - have) {
-                B.err = "truncated BGZF block header";
-                break;
-            }
-        }
+        if (fill(12 + xlen) < 12 + xlen || !io) { B.err = "truncated BGZF block header"; break; }
         const size_t bs = bgzf_block_size(raw.data() + pos, raw.size() - pos);
         if (bs < 12 + xlen + 8) { B.err = "not a BGZF block"; break; }
-        const size_t have = raw.size() - pos;
-        raw.resize(pos + bs);
-        if (!read_full(fd, raw.data() + pos + have, bs - have, got) || got < bs - have) {
-            B.err = "truncated BGZF block";
-            break;
-        }
-        boff.push_back(pos);
-        bsz.push_back(bs);
+        if (fill(bs) < bs || !io) { B.err = "truncated BGZF block"; break; }
+        const uint8_t *t = raw.data() + pos + bs - 8;
+        const uint64_t out = blocks.empty() ? 0 : blocks.back().out + blocks.back().isize;
+        blocks.push_back({pos, bs, pos + 12 + xlen, bs - 12 - xlen - 8, le32(t), le32(t + 4), out});
         pos += bs;
         submit(false);
     }
+    submit(true);
+}
+
+// Step 2: the device's part ends here (after a read error too: it must be done with the batch buffer);
+// on_cpu marks the blocks the CPU inflates -- all of them, or those the GPU refused.  True if the
+// device's blocks are in the batch buffer
+bool finish_device(GpuInflate *dev, size_t nb, std::vector<uint8_t> &on_cpu) {
     bool on_gpu = false;
-    int64_t t2 = 0;
-    if (gpu) {                                 // (after an error too: the device must be done with B.out)
-        submit(true);
-        const int64_t t1 = now_ns();
-        gi->read_ns += t1 - t0;
+    if (dev) {
         fc2::cpu::Scope acct(fc2::cpu::INFLATE);
-        on_gpu = fc2::inf::gpu_finish(gi->g, gi->err);
-        if (!on_gpu) gi->failed = true;        // (the CPU inflates every block of this batch and the next)
-        t2 = now_ns();
-        gi->wait_ns += t2 - t1;
+        on_gpu = fc2::inf::gpu_finish(dev->g, dev->err);
+        if (!on_gpu) dev->failed = true;       // (the CPU inflates every block of this batch and the next)
     }
-    if (gi) gi->read_bytes += pos;
-    if (!B.err.empty()) return B;
-    const size_t nb = boff.size();
-    std::vector<size_t> ooff(nb + 1, 0);
+    on_cpu.assign(nb, on_gpu ? 0 : 1);
+    for (size_t i = 0; on_gpu && i < nb; ++i) on_cpu[i] = fc2::inf::gpu_status(dev->g, i) != 0;
+    return on_gpu;
+}
+
+// the record lists of a batch of n bytes, every block's still empty: the blocks' places from the table
+std::shared_ptr<RecLists> new_lists(const std::vector<Block> &blocks, size_t n, bool gpu) {
+    auto R = std::make_shared<RecLists>();
+    R->n = n;
+    R->ooff.reserve(blocks.size() + 1);
+    for (const Block &b : blocks) R->ooff.push_back(b.out);
+    R->ooff.push_back(n);
+    R->starts.resize(blocks.size());
+    R->exit.assign(blocks.size(), kNoExit);
+    R->gpu = gpu;
+    return R;
+}
+
+// Step 3: the record lists of the blocks the device inflated are the device's -- its rows, moved to
+// batch offsets -- and with digest so are the digest rows of the listed starts, block after block
+void take_device_lists(const fc2::inf::Gpu *g, const std::vector<uint8_t> &on_cpu, bool digest, RecLists &R) {
+    fc2::cpu::Scope acct(fc2::cpu::INFLATE);
+    const size_t nb = on_cpu.size();
+    if (digest) R.row0.assign(nb, kNoRows);
     for (size_t i = 0; i < nb; ++i) {
-        const uint8_t *t = raw.data() + boff[i] + bsz[i] - 4;
-        ooff[i + 1] = ooff[i] + (size_t)(t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24));
+        if (on_cpu[i]) continue;
+        uint32_t cnt, ex;
+        const uint16_t *row = fc2::inf::gpu_walk(g, i, cnt, ex);
+        std::vector<uint32_t> &st = R.starts[i];
+        st.resize(cnt);
+        for (uint32_t k = 0; k < cnt; ++k) st[k] = (uint32_t)R.ooff[i] + row[k];
+        R.exit[i] = ex == FC2_BAM_WALK_NO_EXIT ? kNoExit : R.ooff[i] + (uint64_t)ex;
+        const fc2_bam_digest *rows = digest ? fc2::inf::gpu_digest(g, i, cnt) : nullptr;
+        if (!rows || cnt != st.size()) continue;
+        R.row0[i] = R.rows.size();
+        R.rows.insert(R.rows.end(), rows, rows + cnt);
     }
-    B.n = ooff[nb];
-    B.out.resize(kHead + B.n);
-    // the blocks the CPU inflates: all of them, or those the GPU refused
-    std::vector<uint8_t> on_cpu(nb, on_gpu ? 0 : 1);
-    size_t n_cpu = on_gpu ? 0 : nb;
-    if (on_gpu)
-        for (size_t i = 0; i < nb; ++i)
-            if (fc2::inf::gpu_status(gi->g, i) != 0) on_cpu[i] = 1, ++n_cpu;
-    // every block's records listed by the thread that inflated it, while they are in its cache
-    RecLists *R = nullptr;
-    if (B.n < (uint64_t(1) << 32) && nb) {
-        B.recs = std::make_shared<RecLists>();
-        R = B.recs.get();
-        R->n = B.n;
-        R->ooff = ooff;
-        R->starts.resize(nb);
-        R->exit.assign(nb, kNoExit);
-        R->gpu = on_gpu;
-    }
-    // ... or, for the blocks the device inflated, by the device: its rows, moved to batch offsets
-    const bool listed = R && on_gpu && dev_lists;
-    if (listed) {
-        fc2::cpu::Scope acct(fc2::cpu::INFLATE);
-        for (size_t i = 0; i < nb; ++i) {
-            if (on_cpu[i]) continue;
-            uint32_t cnt, ex;
-            const uint16_t *row = fc2::inf::gpu_walk(gi->g, i, cnt, ex);
-            std::vector<uint32_t> &st = R->starts[i];
-            st.resize(cnt);
-            for (uint32_t k = 0; k < cnt; ++k) st[k] = (uint32_t)ooff[i] + row[k];
-            R->exit[i] = ex == FC2_BAM_WALK_NO_EXIT ? kNoExit : ooff[i] + (uint64_t)ex;
-        }
-        if (dev_digest) {                       // the rows of the listed starts, block after block
-            R->row0.assign(nb, kNoRows);
-            for (size_t i = 0; i < nb; ++i) {
-                if (on_cpu[i]) continue;
-                uint32_t cnt;
-                const fc2_bam_digest *rows = fc2::inf::gpu_digest(gi->g, i, cnt);
-                if (!rows || cnt != R->starts[i].size()) continue;
-                R->row0[i] = R->rows.size();
-                R->rows.insert(R->rows.end(), rows, rows + cnt);
-            }
-        }
-    }
+}
+
+// Step 4: nt threads inflate the blocks marked on_cpu into out (CRC-32 and ISIZE checked) and, with R,
+// list the records of every block not `listed` by the device -- each by the thread that inflated it,
+// while it is in its cache.  False: a corrupt block
+bool inflate_on_cpu(const uint8_t *raw, const std::vector<Block> &blocks, const std::vector<uint8_t> &on_cpu, bool listed,
+                    RecLists *R, char *out, int nt) {
     std::atomic<size_t> next{0};
     std::atomic<bool> bad{false};
     auto work = [&]() {
         fc2::cpu::Scope acct(fc2::cpu::INFLATE);
         fc2::dfl::Inflater inf;                 // libdeflate (zlib without it): fc2_deflate.h
         if (!inf.ok()) { bad = true; return; }
-        for (size_t i; (i = next.fetch_add(1)) < nb && !bad;) {
+        for (size_t i; (i = next.fetch_add(1)) < blocks.size() && !bad;) {
             if (listed && !on_cpu[i]) continue;
-            char *dst = B.out.data() + kHead + ooff[i];
-            const size_t n = ooff[i + 1] - ooff[i];
-            if (on_cpu[i]) {
-                const uint8_t *blk = raw.data() + boff[i];
-                const size_t xl = blk[10] | (blk[11] << 8);
-                const uint8_t *t = blk + bsz[i] - 8;
-                const uint32_t crc = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
-                if (!inf.exact(blk + 12 + xl, bsz[i] - 12 - xl - 8, dst, n) || fc2::dfl::crc32(dst, n) != crc) {
-                    bad = true;
-                    break;
-                }
+            const Block &b = blocks[i];
+            char *dst = out + b.out;
+            if (on_cpu[i] && (!inf.exact(raw + b.payload, b.len, dst, b.isize) || fc2::dfl::crc32(dst, b.isize) != b.crc)) {
+                bad = true;
+                break;
             }
-            if (R) walk_block(B.out.data() + kHead, ooff[i], ooff[i + 1], R->starts[i], R->exit[i]);
+            if (R) walk_block(out, b.out, b.out + b.isize, R->starts[i], R->exit[i]);
         }
     };
-    // (the threads: as many as there are blocks the CPU must still inflate or walk -- none for a batch
-    // the device inflated and listed whole)
-    const int nt = (int)std::min<size_t>((size_t)n_threads, R && !listed ? nb : n_cpu);
     std::vector<std::thread> pool;
     for (int t = 1; t < nt; ++t) pool.emplace_back(work);
     if (nt > 0) work();
     for (auto &t : pool) t.join();
-    if (bad) B.err = "corrupt BGZF block";
-    if (gpu) {                                 // (the batches the GPU took: its blocks, and those it refused)
-        gi->gpu_blocks += nb - n_cpu;
-        gi->cpu_blocks += n_cpu;
-        gi->walk_dev_blocks += listed ? nb - n_cpu : 0;
-        gi->walk_cpu_blocks += !R ? 0 : listed ? n_cpu : nb;
-        gi->cpu_ns += now_ns() - t2;
+    return !bad;
+}
+
+// reads up to `max_blocks` blocks (the first `pre` bytes of the first header are in `pre`)
+BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_threads, std::shared_ptr<GpuInflate> gi) {
+    BgzfBatch B;
+    std::vector<uint8_t> raw, on_cpu;
+    std::vector<Block> blocks;
+    raw.swap(pre);
+    // the GPU inflates the batch in chunks as they are read, into the batch buffer itself -- a pinned
+    // one from the pool, made max_blocks * 64 KiB long up front
+    GpuInflate *dev = batch_on_device(gi.get(), max_blocks) ? gi.get() : nullptr;
+    const bool dev_lists = dev && dev->walk.load(), dev_digest = dev_lists && dev->digest.load();
+    const int64_t t0 = now_ns();
+    if (dev) {
+        B.out.resize(kHead + (size_t)max_blocks * 65536);
+        fc2::inf::gpu_begin(dev->g, B.out.data() + kHead, dev_lists, dev_digest);
+        dev->batches += 1;
+        dev->pinned += fc2::inf::pinned_owns(B.out.data());
+    }
+    read_blocks(fd, max_blocks, raw, blocks, dev, B);
+    const int64_t t1 = now_ns();
+    const bool on_gpu = finish_device(dev, blocks.size(), on_cpu);
+    const int64_t t2 = now_ns();
+    const size_t nb = blocks.size(), n_cpu = (size_t)std::count(on_cpu.begin(), on_cpu.end(), 1);
+    if (dev) dev->read_ns += t1 - t0, dev->wait_ns += t2 - t1;
+    if (gi) gi->read_bytes += nb ? blocks.back().at + blocks.back().size : 0;
+    if (!B.err.empty()) return B;
+    B.n = nb ? blocks.back().out + blocks.back().isize : 0;
+    B.out.resize(kHead + B.n);
+    if (B.n < (uint64_t(1) << 32) && nb) B.recs = new_lists(blocks, B.n, on_gpu);
+    RecLists *R = B.recs.get();
+    const bool listed = R && on_gpu && dev_lists;
+    if (listed) take_device_lists(dev->g, on_cpu, dev_digest, *R);
+    // (the threads: as many as there are blocks the CPU must still inflate or walk -- none for a batch
+    // the device inflated and listed whole)
+    const int nt = (int)std::min<size_t>((size_t)n_threads, R && !listed ? nb : n_cpu);
+    if (!inflate_on_cpu(raw.data(), blocks, on_cpu, listed, R, B.out.data() + kHead, nt)) B.err = "corrupt BGZF block";
+    if (dev) {                                 // (the batches the GPU took: its blocks, and those it refused)
+        dev->cpu_ns += now_ns() - t2;
+        dev->gpu_blocks += nb - n_cpu;
+        dev->cpu_blocks += n_cpu;
+        dev->walk_dev_blocks += listed ? nb - n_cpu : 0;
+        dev->walk_cpu_blocks += !R ? 0 : listed ? n_cpu : nb;
     }
     return B;
 }
@@ -1066,10 +1098,6 @@ bool scan_bam_tags(Rec &r, const uint8_t *p, const uint8_t *end, TagNote *note =
     return true;
 }
 
-// one BAM record body (b: the bs bytes after block_size) into r; thread-safe (reads only the
-// header's reference names), so parser threads can call it.  ops: CIGAR scratch.  A record whose
-// fields do not fit its block, with an unterminated query name or corrupt aux data is an error, as
-// in htslib's bam_read1 / aux parsing.
 // A tag value from its BAM type and the bits of a digest row (fc2_bam_digest), as scan_bam_tags makes it
 fc2::ing::PyNum digest_tag(uint8_t ty, uint32_t bits) {
     using fc2::ing::PyNum;
@@ -1082,6 +1110,10 @@ fc2::ing::PyNum digest_tag(uint8_t ty, uint32_t bits) {
     }
 }
 
+// one BAM record body (b: the bs bytes after block_size) into r; thread-safe (reads only the
+// header's reference names), so parser threads can call it.  ops: CIGAR scratch.  A record whose
+// fields do not fit its block, with an unterminated query name or corrupt aux data is an error, as
+// in htslib's bam_read1 / aux parsing.
 // With `row` -- the record's digest from the device (state 1, its block_size the record's; the device
 // has made every check below on the same bytes) and no SAM text wanted -- the derived fields are the
 // row's: only the name, the lazy SEQ / QUAL pointers and the fixed fields are read from the record.
@@ -1482,11 +1514,10 @@ void bgzf_split_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
             for (;;) {
                 if (lists && q >= base && q - base < lists->n) {
                     const uint64_t bq = q - base;
-                    const size_t j = (size_t)(std::upper_bound(lists->ooff.begin(), lists->ooff.end(), (size_t)bq) -
-                                              lists->ooff.begin()) - 1;
+                    const size_t j = lists->block_of((size_t)bq);
                     const std::vector<uint32_t> &S = lists->starts[j];
-                    const auto it = std::lower_bound(S.begin(), S.end(), (uint32_t)bq);
-                    if (it != S.end() && *it == bq) {
+                    const auto it = lists->listed(j, (size_t)bq);
+                    if (it != S.end()) {
                         const uint64_t tb = beg + A.block - base;   // > bq: q - beg < A.block here
                         const auto c = std::lower_bound(it + 1, S.end(), (uint32_t)std::min<uint64_t>(tb, UINT32_MAX));
                         if (c != S.end() && *c >= tb) { q = base + *c; ++A.split_jumps; break; }
@@ -1572,20 +1603,8 @@ void sam_parse_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
             if (b->n == b->recs.size()) b->recs.emplace_back();
             const fc2_bam_digest *row = nullptr;
             if (rows && p >= lorg && (size_t)(p - lorg) < L->n) {
-                const size_t bq = (size_t)(p - lorg);
-                const size_t nbk = L->starts.size();
-                if (bq < L->ooff[lj] || bq >= L->ooff[lj + 1]) {
-                    if (lj + 1 < nbk && bq >= L->ooff[lj + 1] && bq < L->ooff[lj + 2]) ++lj;
-                    else lj = (size_t)(std::upper_bound(L->ooff.begin(), L->ooff.end(), bq) - L->ooff.begin()) - 1;
-                    lk = 0;
-                }
-                const std::vector<uint32_t> &S = L->starts[lj];
-                if (lk < S.size() && S[lk] > bq) lk = 0;    // (never on a chain of growing offsets)
-                while (lk < S.size() && S[lk] < bq) ++lk;
-                if (lk < S.size() && S[lk] == bq && L->row0[lj] != kNoRows) {
-                    const fc2_bam_digest *c = &L->rows[L->row0[lj] + lk];
-                    if (c->state == 1 && c->block_size == (uint32_t)bs) row = c;
-                }
+                const fc2_bam_digest *c = L->seek(lj, lk, (size_t)(p - lorg)) ? L->row(lj, lk) : nullptr;
+                if (c && c->state == 1 && c->block_size == (uint32_t)bs) row = c;
             }
             const int rc = parse_bam_body(h, (const uint8_t *)p + 4, bs, b->recs[b->n], ps.ops, h->need_text, false,
                                           !h->need_text, row);
@@ -2070,6 +2089,31 @@ extern "C" int fc2_ingest_format(const fc2_ingest *h, int *compression) {
     return h->bam ? FC2_INGEST_BAM : FC2_INGEST_SAM;
 }
 
+// The GPU inflate of h's batches on `device`: its buffers and the first pinned batch buffers made now
+// (after_bytes == 0: in the background while the first batches are read and inflated on the CPU, or,
+// with wait, before this returns), or once after_bytes of the input were read
+static std::shared_ptr<GpuInflate> make_gpu_inflate(const fc2_ingest *h, int device, uint64_t after_bytes, bool wait) {
+    auto gi = std::make_shared<GpuInflate>();
+    gi->device = device;
+    gi->walk = h->gpu_walk;
+    gi->digest = h->gpu_digest;
+    // batches of 1024 blocks (64 MiB inflated, four chunks of 256; fc2_inflate.hip) once the GPU
+    // inflates; FC2_BGZF_BATCH still rules
+    gi->max_blocks = getenv("FC2_BGZF_BATCH") ? (uint32_t)h->bgzf_blocks : 1024u;
+    if (after_bytes) {
+        gi->launched = false;
+        gi->start_after = after_bytes;
+        return gi;
+    }
+    gi->launch(wait);
+    if (wait) {
+        auto r = gi->opening.get();
+        gi->g = r.first;
+        if (!gi->g) gi->failed = true, gi->err = r.second;
+    }
+    return gi;
+}
+
 extern "C" int fc2_ingest_set_gpu_inflate_from(fc2_ingest *h, int device, uint64_t after_bytes) {
     if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_inflate: null argument");
     if (h->n_records) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_inflate: call before reading");
@@ -2080,27 +2124,7 @@ extern "C" int fc2_ingest_set_gpu_inflate_from(fc2_ingest *h, int device, uint64
         h->gpu_inflate.reset();
         return FC2_OK;
     }
-    auto gi = std::make_shared<GpuInflate>();
-    gi->device = device;
-    gi->walk = h->gpu_walk;
-    gi->digest = h->gpu_digest;
-    // batches of 1024 blocks (64 MiB inflated, four chunks of 256; fc2_inflate.hip) once the GPU
-    // inflates; FC2_BGZF_BATCH still rules
-    gi->max_blocks = getenv("FC2_BGZF_BATCH") ? (uint32_t)h->bgzf_blocks : 1024u;
-    if (after_bytes == 0) {
-        // the device's buffers and the first pinned batch buffers: now, or made while the first
-        // batches are read and inflated on the CPU
-        gi->launch(wait);
-        if (wait) {
-            auto r = gi->opening.get();
-            gi->g = r.first;
-            if (!gi->g) gi->failed = true, gi->err = r.second;
-        }
-    } else {
-        gi->launched = false;
-        gi->start_after = after_bytes;
-    }
-    h->gpu_inflate = gi;
+    h->gpu_inflate = make_gpu_inflate(h, device, after_bytes, wait);
     return FC2_OK;
 }
 
@@ -2114,16 +2138,7 @@ extern "C" int fc2_ingest_set_gpu_inflate(fc2_ingest *h, int device, int wait) {
         h->gpu_inflate.reset();
         return FC2_OK;
     }
-    auto gi = std::make_shared<GpuInflate>();
-    gi->device = device;
-    gi->walk = h->gpu_walk;
-    gi->digest = h->gpu_digest;
-    gi->max_blocks = getenv("FC2_BGZF_BATCH") ? (uint32_t)h->bgzf_blocks : 1024u;
-    gi->launch(true);
-    auto r = gi->opening.get();
-    gi->g = r.first;
-    if (!gi->g) gi->failed = true, gi->err = r.second;
-    h->gpu_inflate = gi;
+    h->gpu_inflate = make_gpu_inflate(h, device, 0, true);
     return FC2_OK;
 }
 

@@ -2,7 +2,8 @@
 DEFLATE form zlib writes (stored, fixed and dynamic Huffman codes, every level and strategy), the
 blocks of real BGZF BAMs (fc2_sam_to_bam at level 1, the test BGZF writer at level 6), long and
 overlapping matches, empty and full 64-KiB blocks; and damaged payloads, which must end in a status
-word (never a fault), the host then checking CRC-32 and size as it does for the CPU inflate."""
+word (never a fault); CRC-32 and size are checked on the device too, the host checking them only on
+the blocks it inflates itself."""
 import os
 import zlib
 
@@ -178,6 +179,40 @@ def test_ingest_gpu_inflate_equals_cpu(tmp_path, monkeypatch, batch):
         assert cpu[2] == (0, 0)
 
 
+def test_ingest_gpu_inflate_oversized_member_in_a_chunked_batch(tmp_path, monkeypatch):
+    """A gzip member that inflates to more than BGZF's 64 KiB (htslib reads such members) in the first
+    chunk of a GPU batch of three chunks, 499 in-spec blocks behind it in the batch: the blocks lie in
+    the batch at the sums of the true ISIZEs before them, on the device as on the host, so from the
+    oversized member on the batch is the CPU's, and the fragments and counts are the CPU inflate's
+    (when the device summed min(ISIZE, 64 KiB) instead, the later chunks' bytes lay where the host did
+    not read them and this input ended in a BAM format error).
+    The input is the `tiny` BAM of _bams() (700-byte blocks, level 1) with 100 of its blocks joined
+    into one member.  The member is block 716 of the file, not one of its first 256: with batches of
+    600 the first 616 blocks are read before set_gpu_inflate takes effect (see
+    test_ingest_gpu_inflate_equals_cpu), so that is the first chunk of the first batch the GPU takes."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from samgen import bgzf_compress
+    monkeypatch.setenv("FC2_BGZF_BATCH", "600")
+    data = _raw_rich_bam(tmp_path)
+    a = 700 * (16 + 600 + 100)
+    b = a + 70000
+    big = bgzf_compress(data[a:b], block=b - a, level=1)[:-28]
+    assert len(big) <= 65536 and len(_bgzf_blocks(big)) == 1
+    packed = bgzf_compress(data[:a], block=700, level=1)[:-28] + big + bgzf_compress(data[b:], block=700, level=1)
+    blocks = _bgzf_blocks(packed)
+    assert blocks[716][1] == 70000 and all(isize <= 700 for _, isize, _ in blocks[:716] + blocks[717:])
+    assert len(blocks) >= 616 + 2 * 600                   # the spilled batch whole, and one more for the GPU
+    bam = str(tmp_path / "oversized.bam")
+    open(bam, "wb").write(packed)
+    cpu = _read_all(bam)
+    gpu = _read_all(bam, 0)
+    assert isinstance(cpu[0], list) and cpu[0], cpu
+    print("inflate counts (GPU blocks, CPU blocks):", gpu[2])
+    assert gpu[:2] == cpu[:2]
+    assert gpu[2] is not None and gpu[2][0] > 0 and gpu[2][1] > 0, gpu[2]
+
+
 def _block_spans(raw: bytes):
     """(start, size) of every block of a BGZF file, its 'BC' subfield found among any others."""
     out, pos = [], 0
@@ -303,8 +338,8 @@ def test_ingest_gpu_inflate_from_a_threshold(tmp_path, monkeypatch):
 
 
 def test_ingest_gpu_inflate_corrupt_block_same_error(tmp_path, monkeypatch):
-    """A damaged block: the same error with the GPU inflate as with the CPU's (the host's CRC check
-    and CPU retry stand behind every GPU block)."""
+    """A damaged block: the same error with the GPU inflate as with the CPU's (the device checks each
+    block's CRC-32 and ISIZE and refuses this one; the CPU retry, which checks them itself, reports it)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     monkeypatch.setenv("FC2_BGZF_BATCH", "4")
