@@ -1,7 +1,8 @@
 """The GPU DEFLATE compressor (fc2_deflate_launch, csrc/fc2_deflate.hip) against zlib: every tile's
 stream, inflated alone, gives the tile's bytes and ends where out_len says; the CRC-32 is zlib's;
 nothing outside a tile's own bytes of its slot is written; the project's GPU inflater reads the
-streams back; two launches give the same bytes.  Sizes show that both halves are real: repeats are
+streams back; two launches give the same bytes, and they are the host model's (deflate_model.py) for
+inputs up to 70 KB.  Sizes show that both halves are real: repeats are
 found (a periodic text shrinks far below what Huffman codes alone reach), Huffman codes are built
 (random ACGT shrinks below what fixed codes reach), and what does not shrink is stored."""
 import zlib
@@ -9,7 +10,8 @@ import zlib
 import numpy as np
 import pytest
 
-from deflate_helpers import E_PARAM, check_streams, deflate_launch, fastq_text, tile_bound
+from deflate_helpers import CONTENTS, E_PARAM, check_streams, deflate_launch, fastq_text, tile_bound
+from deflate_model import model
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -22,27 +24,16 @@ def _rng():
     return np.random.default_rng(2024)
 
 
-def _line100():
-    return bytes(_rng().integers(0, 256, 100, dtype=np.uint8))
-
-
-CONTENTS = {
-    "zeros": lambda n: b"\x00" * n,                      # an overlapping match at distance 1
-    "ab": lambda n: (b"AB" * (n // 2 + 1))[:n],
-    "line100": lambda n: (_line100() * (n // 100 + 1))[:n],
-    "acgt": lambda n: np.frombuffer(b"ACGT", np.uint8)[_rng().integers(0, 4, n)].tobytes(),
-    "random": lambda n: bytes(_rng().integers(0, 256, n, dtype=np.uint8)),
-    "range256": lambda n: (bytes(range(256)) * (n // 256 + 1))[:n],
-    "fastq": lambda n: fastq_text(n),
-}
-
-
 def _run(data, tile, stride=None):
     """One input through the kernel, checked; returns (streams, out_len, crc)."""
     d, ln, cr, stride = deflate_launch(data, tile, stride)
     streams = check_streams(data, tile, d, ln, cr, stride)
     d2, ln2, cr2, _ = deflate_launch(data, tile, stride)       # the same bytes on every run
     assert np.array_equal(d, d2) and np.array_equal(ln, ln2) and np.array_equal(cr, cr2)
+    if len(data) <= 70 * 1024:                                 # the same bytes as the host model's
+        for i, s in enumerate(streams):
+            want, info = model(data[i * tile:(i + 1) * tile])
+            assert s == want, "tile %d: not the model's %s stream (%d bytes against %d)" % (i, info["kind"], len(s), len(want))
     return streams, ln, cr
 
 
