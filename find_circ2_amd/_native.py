@@ -158,6 +158,7 @@ EXPORTED = [
     "fc2_ingest_set_gpu_inflate", "fc2_ingest_set_gpu_inflate_from", "fc2_ingest_inflate_counts",
     "fc2_bam_walk_launch", "fc2_bam_walk_host", "fc2_ingest_set_gpu_walk", "fc2_ingest_walk_counts",
     "fc2_bam_digest_launch", "fc2_bam_digest_host", "fc2_ingest_set_gpu_digest", "fc2_ingest_digest_counts",
+    "fc2_bam_frag_launch", "fc2_bam_frag_host", "fc2_ingest_set_gpu_group", "fc2_ingest_group_counts",
     # include/fc2_caller.h
     "fc2_caller_open", "fc2_caller_set_genome", "fc2_caller_inflate_counts", "fc2_caller_ingest", "fc2_caller_close", "fc2_caller_next",
     "fc2_caller_submit", "fc2_caller_submit_compact", "fc2_caller_submit_long", "fc2_caller_queued", "fc2_caller_take", "fc2_caller_rows", "fc2_caller_write_rows", "fc2_caller_counter", "fc2_caller_stats",
@@ -174,6 +175,8 @@ BAM_WALK_CAP = 1824
 BAM_WALK_NO_EXIT = 0xFFFFFFFF
 # ... and the most blocks of one fc2_bam_digest_launch
 BAM_DIGEST_MAX_BLOCKS = 1024
+# ... and the most records of a fragment the device closes (fc2_bam_frag)
+BAM_FRAG_CAP = 16
 
 
 class BamDigest(ctypes.Structure):
@@ -182,6 +185,12 @@ class BamDigest(ctypes.Structure):
                 ("has_qual", ctypes.c_uint8), ("block_size", ctypes.c_uint32), ("astart", ctypes.c_int32),
                 ("qlen", ctypes.c_int32), ("as_bits", ctypes.c_uint32), ("xs_bits", ctypes.c_uint32),
                 ("aend", ctypes.c_int64)]
+
+
+class BamFrag(ctypes.Structure):
+    """fc2_bam_frag: whether a listed record opens a fragment the device closed, and its counts (8 bytes)."""
+    _fields_ = [("state", ctypes.c_uint8), ("n_records", ctypes.c_uint8), ("n_mates", ctypes.c_uint8),
+                ("n_unmapped", ctypes.c_uint8), ("bytes", ctypes.c_uint32)]
 
 
 class IngestParams(ctypes.Structure):
@@ -330,6 +339,10 @@ def lib() -> ctypes.CDLL:
         "fc2_bam_digest_host": (ctypes.c_int, [vp, u32, u32, P(BamDigest)]),
         "fc2_ingest_set_gpu_digest": (ctypes.c_int, [vp, ctypes.c_int]),
         "fc2_ingest_digest_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
+        "fc2_bam_frag_launch": (ctypes.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]),
+        "fc2_bam_frag_host": (ctypes.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32]),
+        "fc2_ingest_set_gpu_group": (ctypes.c_int, [vp, ctypes.c_int]),
+        "fc2_ingest_group_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "fc2_caller_inflate_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "fc2_ctx_create": (ctypes.c_int, [ctypes.c_int, P(vp)]),
         "fc2_ctx_create_sibling": (ctypes.c_int, [vp, P(vp)]),

@@ -296,6 +296,13 @@ def _gpu_digest():
     return os.environ.get("FC2_GPU_DIGEST") == "1"
 
 
+def _gpu_group():
+    """Whether that GPU also closes the unspliced fragments, so the parse threads step over them (DESIGN.md
+    §5 "Unspliced fragments closed on the device"): 1 only with FC2_GPU_GROUP=1 -- off by default, and off
+    at 0 or any other value."""
+    return 1 if os.environ.get("FC2_GPU_GROUP") == "1" else 0
+
+
 def _gzip_device(options):
     """spliced_reads.fastq.gz compressed on the GPU: only with FC2_GPU_GZIP=1, on the first of
     the run's devices, in tiles of FC2_GPU_GZIP_TILE bytes (32768), waiting at most
@@ -332,6 +339,7 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                       **(dict(zip(("inflate_device", "inflate_after"), _inflate_device(options)), gpu_walk=_gpu_walk(),
                               gpu_digest=_gpu_digest())
                          if genome_eval is not None else {}),
+                      gpu_group=_gpu_group(),
                       **(_gzip_device(options) if genome_eval is not None and reads_gz else {}))
     try:
         try:

@@ -44,12 +44,16 @@ uint32_t gpu_max_blocks(const Gpu *g);
 // With digest (and walk), the listed records' digest rows (bam_digest_kernel, include/fc2_ingest.h) come
 // back too: after gpu_finish, gpu_digest(g, i, count) is block i's `count` rows, one per listed start
 // (nullptr: none -- a batch with a block over 64 KiB, or with more rows than the pinned buffer holds).
-void gpu_begin(Gpu *g, char *dest, bool walk, bool digest);
+// With group (which implies walk), the listed records' fragment rows (bam_frag_kernel) come back the same
+// way: gpu_frags(g, i, count).  The digest kernel then runs whether or not digest is set -- the fragment
+// kernel reads its rows on the device -- but its 32-byte rows are downloaded only with digest.
+void gpu_begin(Gpu *g, char *dest, bool walk, bool digest, bool group);
 bool gpu_add(Gpu *g, const uint8_t *raw, const Block *blocks, size_t i0, size_t i1);
 bool gpu_finish(Gpu *g, std::string &err);
 uint32_t gpu_status(const Gpu *g, size_t i);
 const uint16_t *gpu_walk(const Gpu *g, size_t i, uint32_t &count, uint32_t &exit);
 const fc2_bam_digest *gpu_digest(const Gpu *g, size_t i, uint32_t &count);
+const fc2_bam_frag *gpu_frags(const Gpu *g, size_t i, uint32_t &count);
 
 // a pinned buffer of >= n bytes from the pool (nullptr: no pool, too large, or none left)
 void *pinned_take(size_t n);

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/fc2_ingest.h"
+#include "fc2_bam_frag_impl.h"
 #include "fc2_common.h"
 #include "fc2_devcrc.h"
 #include "fc2_inflate.h"
@@ -713,7 +714,57 @@ __global__ __launch_bounds__(64) void bam_digest_kernel(const uint8_t *__restric
     }
 }
 
+// ---- the fragment rows: unspliced fragments closed on the device (fc2_bam_frag_impl.h) -------------
+// The digest kernel's shape: one wavefront per BGZF block, no LDS, no wait on another workgroup (the
+// digest rows it reads were written by the launch before it on the stream); the lanes stride over the
+// block's listed starts, one head a lane.  A fragment crosses blocks, so the records are read from the
+// chunk's contiguous bytes and the neighbouring records' digest rows are reached through a (block, k)
+// cursor over count[] / starts[] / first[].  The lanes' walks differ in length and their loads are
+// their own; fields are composed from byte loads (a record starts at any byte residue).
+//
+// Bounds.  Loads: a record is read only after frag_load has found its digest row in state 1 and shown
+// its end -- at + 4 + the row's block_size -- to be at most n_bytes and its name to lie inside it; the
+// fixed fields and the name bytes are below that end, so every load is inside [bytes, bytes + n_bytes)
+// whatever bytes and rows hold.  starts / count / first / ooff are read at block indices below n_blocks
+// and start indices below min(count, cap); digest rows below first[j] + min(count[j], cap) <=
+// first[n_blocks].  Loops: the back walk takes at most 5 steps, the forward walk at most
+// FC2_BAM_FRAG_CAP + 1; a step's cursor visits each block and each of a block's starts at most once.
+// Stores: lane k of block i writes only frag_rows[first[i] + k], k < min(count[i], cap).
+
+static_assert(sizeof(fc2_bam_frag) == 8, "a fragment row is 8 bytes");
+
+__global__ __launch_bounds__(64) void bam_frag_kernel(const uint8_t *__restrict__ bytes, uint32_t n_bytes,
+                                                      const uint32_t *__restrict__ ooff, const uint16_t *__restrict__ starts,
+                                                      const uint32_t *__restrict__ count,
+                                                      const fc2_bam_digest *__restrict__ rows,
+                                                      const uint32_t *__restrict__ first, fc2_bam_frag *__restrict__ frag_rows,
+                                                      uint32_t n_blocks) {
+    const uint32_t blk = blockIdx.x, lane = threadIdx.x;
+    const fc2::frag::Tables T{bytes, n_bytes, ooff, starts, count, rows, first, n_blocks};
+    const uint32_t cnt = min(count[blk], kWalkCap);
+    const uint64_t f = first[blk];
+    for (uint32_t k = lane; k < cnt; k += 64u) frag_rows[f + k] = fc2::frag::frag_row(T, blk, k);
+}
+
 }  // namespace
+
+// C ABI (include/fc2_ingest.h): the fragment rows of the record starts listed for n_blocks blocks
+extern "C" int fc2_bam_frag_launch(const uint8_t *bytes, uint32_t n_bytes, const uint32_t *ooff, const uint32_t *isize,
+                                   const uint32_t *status, const uint16_t *starts, const uint32_t *count,
+                                   const fc2_bam_digest *rows, const uint32_t *first, fc2_bam_frag *frag_rows,
+                                   uint32_t n_blocks, void *stream) {
+    (void)isize, (void)status;                  // (the digest rows have taken both into account)
+    if (!n_blocks) return FC2_OK;
+    if ((!bytes && n_bytes) || !ooff || !starts || !count || !rows || !first || !frag_rows)
+        return fc2::fail(FC2_E_PARAM, "fc2_bam_frag_launch: null argument");
+    if (n_blocks > kDigestMaxBlocks) return fc2::fail(FC2_E_PARAM, "fc2_bam_frag_launch: more than 1024 blocks");
+    if (((uintptr_t)rows & 7u) || ((uintptr_t)frag_rows & 7u) || ((uintptr_t)first & 3u))
+        return fc2::fail(FC2_E_PARAM, "fc2_bam_frag_launch: rows must be 8-byte and first 4-byte aligned");
+    hipLaunchKernelGGL(bam_frag_kernel, dim3(n_blocks), dim3(64), 0, (hipStream_t)stream, bytes, n_bytes, ooff, starts, count,
+                       rows, first, frag_rows, n_blocks);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_bam_frag_launch: ") + hipGetErrorString(e));
+}
 
 // C ABI (include/fc2_ingest.h): the digest rows of the record starts listed for n_blocks blocks
 extern "C" int fc2_bam_digest_launch(const uint8_t *bytes, uint32_t n_bytes, const uint32_t *ooff, const uint32_t *isize,
@@ -897,6 +948,11 @@ struct Gpu {
     size_t rows_cap = 0;                       // rows h_rows holds (a batch with more gets no digests)
     std::vector<Chunk> dchunks;                // the chunks that were digested
     bool digest = false, rows_ready = false;
+    // the listed records' fragment rows (bam_frag_kernel), indexed like the digest rows and made by the
+    // first batch that asks for them.  With group the digest kernel runs whether or not its rows are
+    // downloaded (digest): the fragment kernel reads them on the device
+    fc2_bam_frag *d_frags = nullptr, *h_frags = nullptr;
+    bool group = false, frags_ready = false;
     bool pooled = false;
     // the batch under way (gpu_begin .. gpu_finish)
     char *dest = nullptr;
@@ -985,22 +1041,25 @@ uint32_t gpu_max_blocks(const Gpu *g) { return g->max_blocks; }
 // rows a block of the pinned row buffer: 64 KiB of records of 128 bytes or more
 constexpr size_t kRowsPerBlock = 512;
 
-void gpu_begin(Gpu *g, char *dest, bool walk, bool digest) {
+void gpu_begin(Gpu *g, char *dest, bool walk, bool digest, bool group) {
     g->dest = dest;
-    g->walk = walk;
-    g->digest = walk && digest;
-    g->spilled = g->rows_ready = false;
+    g->walk = walk || group;
+    g->digest = g->walk && digest;
+    g->group = group;
+    g->spilled = g->rows_ready = g->frags_ready = false;
     g->dchunks.clear();
     g->n = 0;
     g->chunks = 0;
     g->ok = hipSetDevice(g->device) == hipSuccess;
     g->err = g->ok ? "" : "GPU inflate: hipSetDevice failed";
-    if (g->ok && g->digest && !g->d_rows) {
-        const size_t M = g->max_blocks;
-        g->rows_cap = M * kRowsPerBlock;
+    const size_t M = g->max_blocks;
+    g->rows_cap = M * kRowsPerBlock;
+    if (g->ok && (g->digest || g->group) && !g->d_rows)
         make(g, g->d_rows, M * kWalkCap, false, "device digest rows") && make(g, g->d_first, 2 * M + 1, false, "device row index") &&
-            make(g, g->h_rows, g->rows_cap, true, "pinned digest rows") && make(g, g->h_first, 2 * M + 1, true, "pinned row index");
-    }
+            make(g, g->h_first, 2 * M + 1, true, "pinned row index");
+    if (g->ok && g->digest && !g->h_rows) make(g, g->h_rows, g->rows_cap, true, "pinned digest rows");
+    if (g->ok && g->group && !g->d_frags)
+        make(g, g->d_frags, M * kWalkCap, false, "device fragment rows") && make(g, g->h_frags, g->rows_cap, true, "pinned fragment rows");
 }
 
 constexpr size_t kWord = sizeof(uint32_t);
@@ -1065,6 +1124,11 @@ static bool enqueue_digest(Gpu *g, Chunk ch) {
     if (fc2_bam_digest_launch(g->d_out + ch.o0, (uint32_t)(ch.o1 - ch.o0), g->d.rooff + i0, g->d.isize + i0, g->d.status + i0,
                               g->d_starts + r0, g->d_walk.count + i0, g->d_rows + r0, g->d_first + ch.foff, ch.c, s) != FC2_OK)
         return fail(g, "record digest launch failed");
+    if (g->group &&
+        fc2_bam_frag_launch(g->d_out + ch.o0, (uint32_t)(ch.o1 - ch.o0), g->d.rooff + i0, g->d.isize + i0, g->d.status + i0,
+                            g->d_starts + r0, g->d_walk.count + i0, g->d_rows + r0, g->d_first + ch.foff, g->d_frags + r0, ch.c,
+                            s) != FC2_OK)
+        return fail(g, "fragment row launch failed");
     if (!copy(g, g->h_first + ch.foff, g->d_first + ch.foff, (ch.c + 1) * kWord, hipMemcpyDeviceToHost, s)) return false;
     g->dchunks.push_back(ch);
     return true;
@@ -1088,15 +1152,15 @@ bool gpu_add(Gpu *g, const uint8_t *raw, const Block *blocks, size_t i0, size_t 
     if (!stage_chunk(g, raw, blocks, ch)) return true;
     ch.s = g->chunks++ % kStreams;
     return enqueue_inflate(g, ch) && (!g->walk || enqueue_walk(g, ch)) &&
-           (!g->digest || ch.c > kDigestMaxBlocks || enqueue_digest(g, ch)) && enqueue_download(g, ch);
+           ((!g->digest && !g->group) || ch.c > kDigestMaxBlocks || enqueue_digest(g, ch)) && enqueue_download(g, ch);
 }
 
 bool gpu_finish(Gpu *g, std::string &err) {
     for (int k = 0; k < kStreams; ++k)
         if (hip_ok(g, hipEventRecord(g->done[k], g->stream[k]), "event")) hip_ok(g, hipEventSynchronize(g->done[k]), "kernel");
-    // the digest rows, now that every chunk's first[] says how many there are: a sized download per
-    // chunk on its stream, side by side, then the same wait again
-    if (g->ok && g->digest && !g->spilled && !g->dchunks.empty()) {
+    // the digest rows and the fragment rows, now that every chunk's first[] says how many there are: a
+    // sized download per chunk on its stream, side by side, then the same wait again
+    if (g->ok && (g->digest || g->group) && !g->spilled && !g->dchunks.empty()) {
         uint64_t total = 0;
         for (Chunk &ch : g->dchunks) {
             ch.row0 = total;
@@ -1106,14 +1170,20 @@ bool gpu_finish(Gpu *g, std::string &err) {
             bool used[kStreams] = {};
             for (const Chunk &ch : g->dchunks) {
                 const uint64_t n = std::min<uint64_t>(g->h_first[ch.foff + ch.c], (uint64_t)ch.c * kWalkCap);
-                if (n && copy(g, g->h_rows + ch.row0, g->d_rows + (size_t)ch.i0 * kWalkCap, n * sizeof(fc2_bam_digest),
-                              hipMemcpyDeviceToHost, g->stream[ch.s]))
+                const size_t r0 = (size_t)ch.i0 * kWalkCap;
+                if (!n) continue;
+                if (g->digest && copy(g, g->h_rows + ch.row0, g->d_rows + r0, n * sizeof(fc2_bam_digest), hipMemcpyDeviceToHost,
+                                      g->stream[ch.s]))
+                    used[ch.s] = true;
+                if (g->group && copy(g, g->h_frags + ch.row0, g->d_frags + r0, n * sizeof(fc2_bam_frag), hipMemcpyDeviceToHost,
+                                     g->stream[ch.s]))
                     used[ch.s] = true;
             }
             for (int k = 0; k < kStreams; ++k)
                 if (used[k] && hip_ok(g, hipEventRecord(g->done[k], g->stream[k]), "event"))
                     hip_ok(g, hipEventSynchronize(g->done[k]), "download");
-            g->rows_ready = g->ok;
+            g->rows_ready = g->ok && g->digest;
+            g->frags_ready = g->ok && g->group;
         }
     }
     if (!g->ok) err = g->err;
@@ -1128,18 +1198,31 @@ const uint16_t *gpu_walk(const Gpu *g, size_t i, uint32_t &count, uint32_t &exit
     return g->h_starts + i * kWalkCap;
 }
 
-const fc2_bam_digest *gpu_digest(const Gpu *g, size_t i, uint32_t &count) {
+// block i's place among the downloaded rows: its first row's index and its row count (false: it has none)
+static bool block_rows(const Gpu *g, size_t i, uint64_t &row, uint32_t &count) {
     count = 0;
-    if (!g->rows_ready) return nullptr;
     for (const Chunk &ch : g->dchunks)
         if (i >= ch.i0 && i < ch.i0 + ch.c) {
             const uint32_t *f = g->h_first + ch.foff;
             const uint32_t a = f[i - ch.i0], b = f[i - ch.i0 + 1];
-            if (a > b || b > f[ch.c] || (uint64_t)f[ch.c] > (uint64_t)ch.c * kWalkCap) return nullptr;
+            if (a > b || b > f[ch.c] || (uint64_t)f[ch.c] > (uint64_t)ch.c * kWalkCap) return false;
             count = b - a;
-            return g->h_rows + ch.row0 + a;
+            row = ch.row0 + a;
+            return true;
         }
-    return nullptr;
+    return false;
+}
+
+const fc2_bam_digest *gpu_digest(const Gpu *g, size_t i, uint32_t &count) {
+    uint64_t row;
+    count = 0;
+    return g->rows_ready && block_rows(g, i, row, count) ? g->h_rows + row : nullptr;
+}
+
+const fc2_bam_frag *gpu_frags(const Gpu *g, size_t i, uint32_t &count) {
+    uint64_t row;
+    count = 0;
+    return g->frags_ready && block_rows(g, i, row, count) ? g->h_frags + row : nullptr;
 }
 
 }  // namespace inf

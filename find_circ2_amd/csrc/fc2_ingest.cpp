@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/fc2_ingest.h"
+#include "fc2_bam_frag_impl.h"
 #include "fc2_bamout.h"
 #include "fc2_common.h"
 #include "fc2_cpuacct.h"
@@ -239,6 +240,10 @@ struct RecLists {
     }
     // the digest row of block k's listed start m, of a batch that has rows (null: the block has none)
     const fc2_bam_digest *row(size_t k, size_t m) const { return row0[k] == kNoRows ? nullptr : &rows[row0[k] + m]; }
+    // with fc2_ingest_set_gpu_group, the fragment row of the record at starts[k][m]: frags[frow0[k] + m]
+    std::vector<fc2_bam_frag> frags;
+    std::vector<uint64_t> frow0;
+    const fc2_bam_frag *frag(size_t k, size_t m) const { return frow0[k] == kNoRows ? nullptr : &frags[frow0[k] + m]; }
 };
 
 struct BgzfBatch {
@@ -323,6 +328,9 @@ struct GpuInflate {
     // tags; the records that did, and those the parse threads parsed (of the batches the GPU took)
     std::atomic<bool> digest{false};
     std::atomic<uint64_t> digest_dev_records{0}, digest_host_records{0};
+    // fc2_ingest_set_gpu_group: the listed records' fragment rows (fc2_bam_frag, bam_frag_kernel) come
+    // back as well, and the parse threads step over the fragments they close
+    std::atomic<bool> group{false};
     // FC2_CALLER_TIMING: the batch reader's time reading, submitting chunks, waiting for the device,
     // inflating refused blocks; batches whose buffer was pinned (downloaded into directly)
     int64_t read_ns = 0, add_ns = 0, wait_ns = 0, cpu_ns = 0;
@@ -458,10 +466,11 @@ std::shared_ptr<RecLists> new_lists(const std::vector<Block> &blocks, size_t n, 
 
 // Step 3: the record lists of the blocks the device inflated are the device's -- its rows, moved to
 // batch offsets -- and with digest so are the digest rows of the listed starts, block after block
-void take_device_lists(const fc2::inf::Gpu *g, const std::vector<uint8_t> &on_cpu, bool digest, RecLists &R) {
+void take_device_lists(const fc2::inf::Gpu *g, const std::vector<uint8_t> &on_cpu, bool digest, bool group, RecLists &R) {
     fc2::cpu::Scope acct(fc2::cpu::INFLATE);
     const size_t nb = on_cpu.size();
     if (digest) R.row0.assign(nb, kNoRows);
+    if (group) R.frow0.assign(nb, kNoRows);
     for (size_t i = 0; i < nb; ++i) {
         if (on_cpu[i]) continue;
         uint32_t cnt, ex;
@@ -471,10 +480,41 @@ void take_device_lists(const fc2::inf::Gpu *g, const std::vector<uint8_t> &on_cp
         for (uint32_t k = 0; k < cnt; ++k) st[k] = (uint32_t)R.ooff[i] + row[k];
         R.exit[i] = ex == FC2_BAM_WALK_NO_EXIT ? kNoExit : R.ooff[i] + (uint64_t)ex;
         const fc2_bam_digest *rows = digest ? fc2::inf::gpu_digest(g, i, cnt) : nullptr;
-        if (!rows || cnt != st.size()) continue;
-        R.row0[i] = R.rows.size();
-        R.rows.insert(R.rows.end(), rows, rows + cnt);
+        if (rows && cnt == st.size()) {
+            R.row0[i] = R.rows.size();
+            R.rows.insert(R.rows.end(), rows, rows + cnt);
+        }
+        const fc2_bam_frag *frags = group ? fc2::inf::gpu_frags(g, i, cnt) : nullptr;
+        if (frags && cnt == st.size()) {
+            R.frow0[i] = R.frags.size();
+            R.frags.insert(R.frags.end(), frags, frags + cnt);
+        }
     }
+}
+
+// fc2_ingest_set_gpu_group(h, 2), the test setting: the fragment rows of a batch the CPU inflated and
+// listed, from fc2_bam_frag_host over the whole batch as one chunk
+void host_frag_rows(const char *data, RecLists &R) {
+    const size_t nb = R.starts.size();
+    std::vector<uint32_t> ooff(nb), isize(nb), count(nb), first(nb + 1);
+    std::vector<uint16_t> starts(nb * FC2_BAM_WALK_CAP);
+    size_t total = 0;
+    for (size_t k = 0; k < nb; ++k) {
+        ooff[k] = (uint32_t)R.ooff[k];
+        isize[k] = (uint32_t)(R.ooff[k + 1] - R.ooff[k]);
+        if (isize[k] > 65536 || R.starts[k].size() > FC2_BAM_WALK_CAP || nb > FC2_BAM_DIGEST_MAX_BLOCKS) return;
+        count[k] = (uint32_t)R.starts[k].size();
+        for (size_t m = 0; m < R.starts[k].size(); ++m)
+            starts[k * FC2_BAM_WALK_CAP + m] = (uint16_t)(R.starts[k][m] - ooff[k]);
+        total += count[k];
+    }
+    R.frags.resize(total);
+    if (fc2_bam_frag_host((const uint8_t *)data, (uint32_t)R.n, ooff.data(), isize.data(), nullptr, starts.data(), count.data(),
+                          R.frags.data(), first.data(), (uint32_t)nb) != FC2_OK) {
+        R.frags.clear();
+        return;
+    }
+    R.frow0.assign(first.begin(), first.begin() + (ptrdiff_t)nb);
 }
 
 // Step 4: nt threads inflate the blocks marked on_cpu into out (CRC-32 and ISIZE checked) and, with R,
@@ -507,7 +547,8 @@ bool inflate_on_cpu(const uint8_t *raw, const std::vector<Block> &blocks, const 
 }
 
 // reads up to `max_blocks` blocks (the first `pre` bytes of the first header are in `pre`)
-BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_threads, std::shared_ptr<GpuInflate> gi) {
+BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_threads, std::shared_ptr<GpuInflate> gi,
+                     bool host_frags) {
     BgzfBatch B;
     std::vector<uint8_t> raw, on_cpu;
     std::vector<Block> blocks;
@@ -515,11 +556,12 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
     // the GPU inflates the batch in chunks as they are read, into the batch buffer itself -- a pinned
     // one from the pool, made max_blocks * 64 KiB long up front
     GpuInflate *dev = batch_on_device(gi.get(), max_blocks) ? gi.get() : nullptr;
-    const bool dev_lists = dev && dev->walk.load(), dev_digest = dev_lists && dev->digest.load();
+    const bool dev_group = dev && dev->group.load();
+    const bool dev_lists = dev && (dev->walk.load() || dev_group), dev_digest = dev_lists && dev->digest.load();
     const int64_t t0 = now_ns();
     if (dev) {
         B.out.resize(kHead + (size_t)max_blocks * 65536);
-        fc2::inf::gpu_begin(dev->g, B.out.data() + kHead, dev_lists, dev_digest);
+        fc2::inf::gpu_begin(dev->g, B.out.data() + kHead, dev_lists, dev_digest, dev_group);
         dev->batches += 1;
         dev->pinned += fc2::inf::pinned_owns(B.out.data());
     }
@@ -536,11 +578,12 @@ BgzfBatch bgzf_batch(int fd, std::vector<uint8_t> pre, int max_blocks, int n_thr
     if (B.n < (uint64_t(1) << 32) && nb) B.recs = new_lists(blocks, B.n, on_gpu);
     RecLists *R = B.recs.get();
     const bool listed = R && on_gpu && dev_lists;
-    if (listed) take_device_lists(dev->g, on_cpu, dev_digest, *R);
+    if (listed) take_device_lists(dev->g, on_cpu, dev_digest, dev_group, *R);
     // (the threads: as many as there are blocks the CPU must still inflate or walk -- none for a batch
     // the device inflated and listed whole)
     const int nt = (int)std::min<size_t>((size_t)n_threads, R && !listed ? nb : n_cpu);
     if (!inflate_on_cpu(raw.data(), blocks, on_cpu, listed, R, B.out.data() + kHead, nt)) B.err = "corrupt BGZF block";
+    else if (host_frags && R && !on_gpu) host_frag_rows(B.out.data() + kHead, *R);
     if (dev) {                                 // (the batches the GPU took: its blocks, and those it refused)
         dev->cpu_ns += now_ns() - t2;
         dev->gpu_blocks += nb - n_cpu;
@@ -582,6 +625,10 @@ struct fc2_ingest {
     std::shared_ptr<GpuInflate> gpu_inflate;     // fc2_ingest_set_gpu_inflate (null: the CPU inflates)
     bool gpu_walk = true;                        // fc2_ingest_set_gpu_walk, for a GPU inflate set later
     bool gpu_digest = false;                     // fc2_ingest_set_gpu_digest, likewise
+    // fc2_ingest_set_gpu_group (0 off, 1 the device's rows, 2 rows made on the host: a test setting); the
+    // fragments the parse threads stepped over on those rows' word
+    std::atomic<int> gpu_group{0};
+    std::atomic<uint64_t> group_dev_frags{0};
     std::atomic<int64_t> inflate_wait_ns{0};     // the reader's wait for inflated BGZF batches (timing)
     std::string z_err;
     // header
@@ -763,7 +810,7 @@ bool ensure(fc2_ingest *h, size_t n) {
             if (!b.err.empty()) { h->z_err = b.err; h->z_done = true; return false; }
             if (b.eof) h->z_done = true;
             else h->bgzf_next = std::async(std::launch::async, bgzf_batch, h->fd, std::vector<uint8_t>(), batch_blocks(h),
-                                           h->bgzf_nt, h->gpu_inflate);
+                                           h->bgzf_nt, h->gpu_inflate, false);
             if (h->buf.size() < h->end + b.n) h->buf.resize(h->end + b.n);
             if (b.n) memcpy(h->buf.data() + h->end, b.data(), b.n);
             h->end += b.n;
@@ -1454,7 +1501,7 @@ void bgzf_split_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
         if (!b.err.empty()) { h->z_err = b.err; h->z_done = true; return false; }
         if (b.eof) h->z_done = true;
         else h->bgzf_next = std::async(std::launch::async, bgzf_batch, h->fd, std::vector<uint8_t>(), batch_blocks(h), h->bgzf_nt,
-                                       h->gpu_inflate);
+                                       h->gpu_inflate, h->gpu_group.load() == 2);
         const size_t L = end - beg;
         std::shared_ptr<CharBuf> nb;
         if (L <= kHead) {
@@ -1594,27 +1641,79 @@ void sam_parse_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
         // row where a listed start is its own offset, the row is valid and carries its block_size
         const RecLists *L = b->vbuf && h->bam ? b->lists.get() : nullptr;
         const bool rows = L && !L->rows.empty() && !h->need_text;
-        const char *lorg = rows ? b->vbuf->data() + b->lbase : nullptr;
+        // ... and its fragment rows (fc2_ingest_set_gpu_group): at a listed start whose row says the
+        // device closed the fragment that opens there, the loop steps to the record that opens the next
+        // one and leaves a placeholder for group_batch -- the fragment's bytes are not read.  Only once
+        // the batch holds a real mapped record (group_batch names the batch's first fragment after it),
+        // and only if the next fragment's first record lies in this batch, so a placeholder is always
+        // followed by a real record that closes it.  That the record closes the fragment before it is
+        // known from the rows alone when a placeholder ended exactly here (its forward walk found this
+        // record); after a real record the name is compared with the last mapped record's, one read of
+        // the head's first line: the chain the device walked back on need not be the one this loop is on.
+        const bool frows = A.group && L && !L->frags.empty() && !h->need_text && h->gpu_group.load() != 0;
+        const char *lorg = rows || frows ? b->vbuf->data() + b->lbase : nullptr;
         size_t lj = 0, lk = 0;
-        uint64_t dig_dev = 0, dig_host = 0;
+        uint64_t dig_dev = 0, dig_host = 0, grp_dev = 0;
+        size_t last_mapped = SIZE_MAX;          // the last real mapped record of the batch
+        const char *ph_end = nullptr;           // where the last placeholder's fragment ended
+        const char *run_p = nullptr;            // the placeholders at the batch's tail: the first one's
+        size_t run_n = 0;                       // offset and record index, how many they are
+        uint64_t run_cnt = 0;
+        bool skip = frows;
         while (h->bam && p < end && b->rc == FC2_OK) {     // whole BAM records (bam/bgzf_split_loop)
             int32_t bs;
             memcpy(&bs, p, 4);
             if (b->n == b->recs.size()) b->recs.emplace_back();
+            Rec &rec = b->recs[b->n];
+            rec.ph = 0;
+            const bool at_start = lorg && p >= lorg && (size_t)(p - lorg) < L->n && L->seek(lj, lk, (size_t)(p - lorg));
+            if (skip && at_start && last_mapped != SIZE_MAX) {
+                const fc2_bam_frag *f = L->frag(lj, lk);
+                if (f && f->state == 1 && f->bytes >= 36 && (size_t)f->bytes < (size_t)(end - p)) {
+                    bool closes = p == ph_end;
+                    if (!closes && end - p >= 36) {
+                        const size_t ln = (uint8_t)p[12];
+                        const std::string &q = b->recs[last_mapped].qname;
+                        closes = ln >= 1 && 36 + ln <= (size_t)(end - p) && !(q.size() == ln - 1 && memcmp(q.data(), p + 36, ln - 1) == 0);
+                    }
+                    if (closes) {
+                        if (p != ph_end) run_p = p, run_n = b->n, run_cnt = 0;
+                        rec.ph = 1;
+                        rec.flag = 0;
+                        rec.ph_records = f->n_records, rec.ph_mates = f->n_mates, rec.ph_unmapped = f->n_unmapped;
+                        ++b->n;
+                        p += f->bytes;
+                        ph_end = p;
+                        ++run_cnt, ++grp_dev;
+                        continue;
+                    }
+                }
+            }
             const fc2_bam_digest *row = nullptr;
-            if (rows && p >= lorg && (size_t)(p - lorg) < L->n) {
-                const fc2_bam_digest *c = L->seek(lj, lk, (size_t)(p - lorg)) ? L->row(lj, lk) : nullptr;
+            if (rows && at_start) {
+                const fc2_bam_digest *c = L->row(lj, lk);
                 if (c && c->state == 1 && c->block_size == (uint32_t)bs) row = c;
             }
-            const int rc = parse_bam_body(h, (const uint8_t *)p + 4, bs, b->recs[b->n], ps.ops, h->need_text, false,
-                                          !h->need_text, row);
+            const int rc = parse_bam_body(h, (const uint8_t *)p + 4, bs, rec, ps.ops, h->need_text, false, !h->need_text, row);
+            // Defensive: a row's closer is a record whose digest has state 1, which parse_bam_body accepts, so
+            // this is unreachable while the digest and the parser agree (no test reaches it).  Should they
+            // ever not, the fragments stepped over before the record are parsed after all, and the error is
+            // raised where it is with the feature off
+            if (rc && p == ph_end) {
+                b->n = run_n, p = run_p, grp_dev -= run_cnt;
+                ph_end = nullptr;
+                skip = false;
+                continue;
+            }
             if (rc) { b->rc = rc; b->err = fc2_last_error(); break; }
+            if (!rec.unmapped()) last_mapped = b->n;
             ++b->n;
             p += 4 + (size_t)bs;
             if (L && L->gpu) ++(row ? dig_dev : dig_host);
         }
         if (dig_dev | dig_host)
             if (GpuInflate *gi = h->gpu_inflate.get()) gi->digest_dev_records += dig_dev, gi->digest_host_records += dig_host;
+        h->group_dev_frags += grp_dev;
         b->lists.reset();
         while (!h->bam && p < end && b->rc == FC2_OK) {
             const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
@@ -1625,6 +1724,7 @@ void sam_parse_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
             for (const char *c = ls; c < le; ++c) if (!isspace((unsigned char)*c)) { blank = false; break; }
             if (blank) continue;
             if (b->n == b->recs.size()) b->recs.emplace_back();
+            b->recs[b->n].ph = 0;
             const int rc = parse_sam_record(h, ls, le, b->recs[b->n], ps, !h->need_text);
             if (rc) { b->rc = rc; b->err = fc2_last_error(); break; }
             ++b->n;
@@ -1847,6 +1947,11 @@ int emit_or_count(fc2_ingest *h, const fc2_ingest_params *p, uint64_t &n_handed,
 // parse thread, exactly as the loop would: the fragments closed in [gs, gt) with their counts, the
 // handed ones listed for the sink; the consumer closes the fragment before gs, takes the list, and
 // goes on sequentially from gt (whose record opens the fragment still open at the batch's end).
+// A placeholder (Rec::ph: a fragment the parse loop stepped over on the device's word) stands for a mapped
+// record whose name equals nothing: it closes the fragment before it, and the next record closes it, with
+// the counts it carries in place of eval_mate.  The parse loop leaves one only after a real mapped record
+// and always with a real record behind it, so gs may be a placeholder, gt never is, and no record outside
+// [gs, gt) is one: the consumer's sequential path never meets one.
 void group_batch(const fc2_ingest_params &p, fc2_ingest::SamAhead::Batch &b) {
     using Batch = fc2_ingest::SamAhead::Batch;
     b.gs = b.gt = 0;
@@ -1860,7 +1965,7 @@ void group_batch(const fc2_ingest_params &p, fc2_ingest::SamAhead::Batch &b) {
     while (i < n && R[i].unmapped()) ++i;
     if (i == n) return;
     size_t s = i + 1;
-    while (s < n && (R[s].unmapped() || R[s].qname == R[i].qname)) ++s;
+    while (s < n && !R[s].ph && (R[s].unmapped() || R[s].qname == R[i].qname)) ++s;
     if (s >= n) return;
     struct LM {                                 // a mate: record positions, proper indices
         std::vector<int32_t> r, p;
@@ -1874,7 +1979,8 @@ void group_batch(const fc2_ingest_params &p, fc2_ingest::SamAhead::Batch &b) {
     uint64_t span_cum = 0, arena_cum = 0;
     size_t t = s;
     auto open = [&](LM &m, size_t j) {
-        C.total_mates++;
+        if (R[j].ph) C.total_mates += R[j].ph_mates, C.records += R[j].ph_records - 1u, C.unmapped_reads += R[j].ph_unmapped;
+        else C.total_mates++;
         m.r.clear();
         m.p.clear();
         m.r.push_back((int32_t)j);
@@ -1894,6 +2000,10 @@ void group_batch(const fc2_ingest_params &p, fc2_ingest::SamAhead::Batch &b) {
         C.n_reads++;
         ++F;
         if (p.noop) return;
+        if (R[cur.r[0]].ph) {                   // closed on the device: every mate unspliced, nothing handed
+            C.unspliced_mates += R[cur.r[0]].ph_mates;
+            return;
+        }
         LM *ms[2] = {have_oth ? &oth : nullptr, &cur};
         MateEval ev[2];
         int circ = 0, lin = 0;
@@ -1951,7 +2061,7 @@ void group_batch(const fc2_ingest_params &p, fc2_ingest::SamAhead::Batch &b) {
             continue;
         }
         const Rec &prim = R[cur.r[0]];
-        const bool same = r.qname == prim.qname;
+        const bool same = !r.ph && !prim.ph && r.qname == prim.qname;
         if (same && r.read1() == prim.read1()) {              // add_segment
             C.records++;
             const bool proper = r.tid == prim.tid && r.reverse() == prim.reverse();
@@ -2043,7 +2153,7 @@ extern "C" int fc2_ingest_open(const char *path, int is_bam, fc2_ingest **out) {
             if (const char *e = getenv("FC2_BGZF_BATCH"))
                 if (atoi(e) > 0) h->bgzf_blocks = std::min(atoi(e), 4096);
             h->bgzf_next = std::async(std::launch::async, bgzf_batch, fd, std::move(pre), std::min(16, h->bgzf_blocks),
-                                      h->bgzf_nt, nullptr);
+                                      h->bgzf_nt, nullptr, false);
         } else {
             // any other gzip stream (gzip -c, concatenated members)
             h->src = fc2_ingest::SRC_GZIP;
@@ -2097,6 +2207,7 @@ static std::shared_ptr<GpuInflate> make_gpu_inflate(const fc2_ingest *h, int dev
     gi->device = device;
     gi->walk = h->gpu_walk;
     gi->digest = h->gpu_digest;
+    gi->group = h->gpu_group.load() == 1;
     // batches of 1024 blocks (64 MiB inflated, four chunks of 256; fc2_inflate.hip) once the GPU
     // inflates; FC2_BGZF_BATCH still rules
     gi->max_blocks = getenv("FC2_BGZF_BATCH") ? (uint32_t)h->bgzf_blocks : 1024u;
@@ -2180,6 +2291,51 @@ extern "C" int fc2_ingest_digest_counts(const fc2_ingest *h, uint64_t *device_re
     return FC2_OK;
 }
 
+extern "C" int fc2_ingest_set_gpu_group(fc2_ingest *h, int on) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_group: null argument");
+    if (on < 0 || on > 2) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_group: on is 0, 1 or 2");
+    h->gpu_group = on;
+    if (GpuInflate *gi = h->gpu_inflate.get()) gi->group = on == 1;     // (the batch reader may be running: atomic)
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_group_counts(const fc2_ingest *h, uint64_t *device_fragments, uint64_t *host_fragments) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_group_counts: null argument");
+    // (meaningful at the end of the input: the parse threads count ahead of the consumer's n_reads)
+    const uint64_t dev = h->group_dev_frags.load(), all = h->counts.n_reads;
+    if (device_fragments) *device_fragments = dev;
+    if (host_fragments) *host_fragments = all > dev ? all - dev : 0;
+    return FC2_OK;
+}
+
+// The fragment rows of every listed start, from the rule the kernel compiles (fc2_bam_frag_impl.h) over
+// digest rows made by fc2_bam_digest_host, with the blocks' status applied as bam_digest_kernel applies it
+extern "C" int fc2_bam_frag_host(const uint8_t *bytes, uint32_t n_bytes, const uint32_t *ooff, const uint32_t *isize,
+                                 const uint32_t *status, const uint16_t *starts, const uint32_t *count,
+                                 fc2_bam_frag *frag_rows, uint32_t *first, uint32_t n_blocks) {
+    if (!n_blocks) return FC2_OK;
+    if ((!bytes && n_bytes) || !ooff || !isize || !starts || !count || !frag_rows || !first)
+        return fc2::fail(FC2_E_PARAM, "fc2_bam_frag_host: null argument");
+    if (n_blocks > FC2_BAM_DIGEST_MAX_BLOCKS) return fc2::fail(FC2_E_PARAM, "fc2_bam_frag_host: more than 1024 blocks");
+    first[0] = 0;
+    for (uint32_t j = 0; j < n_blocks; ++j) first[j + 1] = first[j] + std::min<uint32_t>(count[j], FC2_BAM_WALK_CAP);
+    std::vector<fc2_bam_digest> rows(first[n_blocks]);
+    for (uint32_t j = 0; j < n_blocks; ++j)
+        for (uint32_t k = 0; k < first[j + 1] - first[j]; ++k) {
+            fc2_bam_digest &d = rows[first[j] + k];
+            const uint64_t at = (uint64_t)ooff[j] + starts[(size_t)j * FC2_BAM_WALK_CAP + k];
+            memset(&d, 0, sizeof d);
+            if (at > n_bytes || fc2_bam_digest_host(bytes, n_bytes, (uint32_t)at, &d) != FC2_OK || d.state != 1) continue;
+            const uint64_t lim = at + 4 + d.block_size;
+            for (uint32_t b = j; status && b < n_blocks && (b == j || ooff[b] < lim); ++b)
+                if (status[b] != 0) d.state = 0;
+        }
+    const fc2::frag::Tables T{bytes, n_bytes, ooff, starts, count, rows.data(), first, n_blocks};
+    for (uint32_t j = 0; j < n_blocks; ++j)
+        for (uint32_t k = 0; k < first[j + 1] - first[j]; ++k) frag_rows[first[j] + k] = fc2::frag::frag_row(T, j, k);
+    return FC2_OK;
+}
+
 // The digest row of one record start, from parse_bam_body itself (the form of the device's rows,
 // fc2_bam_digest_launch): what the parser leaves in a Rec, the tags' types and counts from
 // scan_bam_tags' note, and cigar_info's 64-bit sums for the records whose sums the row cannot hold
@@ -2249,6 +2405,12 @@ fc2_ingest::~fc2_ingest() { ahead.reset(); }
 extern "C" void fc2_ingest_close(fc2_ingest *h) {
     if (!h) return;
     h->ahead.reset();                  // stops the parse-ahead thread before the fd goes
+    if (h->gpu_group.load() && getenv("FC2_CALLER_TIMING")) {
+        uint64_t dev = 0, host = 0;
+        fc2_ingest_group_counts(h, &dev, &host);
+        fprintf(stderr, "gpu group: %llu fragments closed on the device, %llu grouped on the host\n", (unsigned long long)dev,
+                (unsigned long long)host);
+    }
     if (h->bam_out) {
         std::string err;
         fc2::bam::close_writer(h->bam_out, err);

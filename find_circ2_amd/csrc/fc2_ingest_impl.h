@@ -67,6 +67,10 @@ struct Rec : RecFields {
     std::string seq, qual;  // SEQ / QUAL (see decode())
     uint32_t seq_n = 0;    // seq.size() once decoded ("*" counts 1, as the string does)
     LazySeq lz;
+    // A placeholder a parse thread left for a whole fragment it stepped over (fc2_bam_frag, state 1): no
+    // field above is set; group_batch reads it as a mapped record whose name equals nothing, closed by the
+    // next record with these counts.  Stays with its batch slot (not swapped), reset by every parse.
+    uint8_t ph = 0, ph_records = 0, ph_mates = 0, ph_unmapped = 0;
     bool unmapped() const { return flag & 0x4; }
     bool read1() const { return flag & 0x40; }
     bool reverse() const { return flag & 0x10; }

@@ -94,6 +94,20 @@ class NativeIngest:
         N.check(N.lib().fc2_ingest_digest_counts(self.h, ctypes.byref(d), ctypes.byref(c)))
         return int(d.value), int(c.value)
 
+    def set_gpu_group(self, on: int):
+        """Whether the parse threads step over the fragments the device closed -- those whose mates each have
+        fewer than two proper segments, found by the GPU that inflated and listed their records
+        (fc2_ingest_set_gpu_group) -- or group every record themselves (0, the default).  2 is a test
+        setting: the rows are made on the host for the batches the CPU inflates."""
+        N.check(N.lib().fc2_ingest_set_gpu_group(self.h, int(on)))
+
+    def group_counts(self) -> Tuple[int, int]:
+        """(fragments the parse threads stepped over on the device's word, every other fragment); read it
+        once the input is exhausted (the parse threads count ahead of the reader)."""
+        d, c = ctypes.c_uint64(), ctypes.c_uint64()
+        N.check(N.lib().fc2_ingest_group_counts(self.h, ctypes.byref(d), ctypes.byref(c)))
+        return int(d.value), int(c.value)
+
     def close_bam_out(self):
         N.check(N.lib().fc2_ingest_close_bam_out(self.h))
 

@@ -74,7 +74,7 @@ class NativeCaller:
                  write_multi=True, genome_dummy=False, known_circ: str = "", known_lin: str = "",
                  bam_out: str = "", reads_gz=None, inflate_device=None, inflate_after: int = 0,
                  gzip_device=None, gzip_tile: int = 0, gzip_timeout_s: float = 0.0, gpu_walk: bool = True,
-                 gpu_digest: bool = False):
+                 gpu_digest: bool = False, gpu_group: int = 0):
         o = copts
         # the strings must outlive the handle's open call (fc2_caller_open copies them)
         self._keep = [o.name.encode(), known_circ.encode() if known_circ else None,
@@ -97,6 +97,7 @@ class NativeCaller:
         self.inflate_after = inflate_after     # ... once this many bytes of the input were read
         self.gpu_walk = gpu_walk               # ... their BAM record starts listed there too (else by host threads)
         self.gpu_digest = gpu_digest           # ... and the listed records' derived fields computed there (else parsed)
+        self.gpu_group = int(gpu_group)        # ... and the unspliced fragments closed there (2: on the host, a test setting)
         self.gzip_device = gzip_device         # spliced_reads.fastq.gz compressed on this GPU (None: the worker threads)
         self.gzip_tile = gzip_tile             # ... in tiles of this many bytes (0: 32768), each a gzip member
         self.gzip_timeout_s = gzip_timeout_s   # ... waiting at most this long for the device (0: 60 s)
@@ -120,6 +121,8 @@ class NativeCaller:
             N.check(L.fc2_ingest_set_gpu_inflate_from(ing, int(self.inflate_device), int(self.inflate_after)))
             N.check(L.fc2_ingest_set_gpu_walk(ing, int(bool(self.gpu_walk))))
             N.check(L.fc2_ingest_set_gpu_digest(ing, int(bool(self.gpu_digest))))
+        if self.gpu_group:
+            N.check(L.fc2_ingest_set_gpu_group(ing, self.gpu_group))
         if self.reads_gz:
             path, level, threads, piece = self.reads_gz
             N.check(L.fc2_caller_set_reads_gz(self.h, path.encode(), int(level), int(threads), int(piece)))
@@ -157,6 +160,14 @@ class NativeCaller:
         d, c = ctypes.c_uint64(), ctypes.c_uint64()
         L = N.lib()
         N.check(L.fc2_ingest_digest_counts(L.fc2_caller_ingest(self.h), ctypes.byref(d), ctypes.byref(c)))
+        return int(d.value), int(c.value)
+
+    def group_counts(self):
+        """(fragments the parse threads stepped over because the device had closed them, every other
+        fragment), to be read once the input is exhausted (fc2_ingest_group_counts); (0, n) without gpu_group."""
+        d, c = ctypes.c_uint64(), ctypes.c_uint64()
+        L = N.lib()
+        N.check(L.fc2_ingest_group_counts(L.fc2_caller_ingest(self.h), ctypes.byref(d), ctypes.byref(c)))
         return int(d.value), int(c.value)
 
     def reads_gz_counts(self):

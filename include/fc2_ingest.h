@@ -178,6 +178,62 @@ int fc2_bam_digest_host(const uint8_t *bytes, uint32_t n_bytes, uint32_t at, fc2
 int fc2_ingest_set_gpu_digest(fc2_ingest *h, int on);
 /* Records of the batches the GPU inflated whose fields came from device rows, and those the host parsed. */
 int fc2_ingest_digest_counts(const fc2_ingest *h, uint64_t *device_records, uint64_t *host_records);
+
+/* The fragment row: whether the record at a listed start opens a fragment that is never handed to the
+ * search whatever the options are -- each mate has fewer than two proper segments, so the fragment changes
+ * four counters and nothing else -- and where the next fragment begins, found on the GPU (fc2_inflate.hip
+ * bam_frag_kernel) from the bytes the walk and the digest read.  One row per listed start, indexed like
+ * the digest rows.  The ingest's parse threads step over such a fragment without building its records. */
+typedef struct fc2_bam_frag {
+    uint8_t  state;       /* 1: this record opens a fragment the device closed; 0: nothing is claimed */
+    uint8_t  n_records;   /* records of the fragment, this one and unmapped ones included */
+    uint8_t  n_mates;     /* 1 or 2 */
+    uint8_t  n_unmapped;  /* records among them with flag & 4 */
+    uint32_t bytes;       /* from this record's offset to the offset of the record that opens the next fragment */
+} fc2_bam_frag;
+/* Records of a fragment the device closes, at most. */
+#define FC2_BAM_FRAG_CAP 16
+/* The tables of fc2_bam_digest_launch, the digest rows it made of them (rows, first: device memory, the
+ * launch before this one on `stream`), and frag_rows[first[i] + k] for block i's k-th listed start.
+ * isize and status are taken to keep that launch's argument list and are not read: a block's status acts
+ * here only through the digest rows, where a record that touches a refused block has state 0.
+ * A record is *usable* if its digest row has state 1.  A step from a record forward reaches the record at
+ * its end (offset + 4 + block_size), which must be a listed start and usable; a step back reaches the
+ * listed start before it in the order of the lists, which must be usable and end where this one starts.
+ * Two names are equal when l_read_name and the l_read_name - 1 bytes before the NUL are.  Record H gets
+ * state 1 only if (otherwise the row is all zeros)
+ *   1. H is usable and mapped (flag & 4 == 0);
+ *   2. stepping back over at most 4 unmapped records reaches a mapped record, whose name differs from H's;
+ *   3. stepping forward reaches a mapped record N whose name differs from H's, after at most
+ *      FC2_BAM_FRAG_CAP records (H, and every record before N: the fragment);
+ *   4. the fragment's mapped records form one or two mates: H opens mate 1, a record whose flag & 0x40 is
+ *      the current mate's first record's is a segment of it, the first one that differs opens mate 2, and
+ *      a further change ends the attempt;
+ *   5. no segment is proper (the refID and the flag & 0x10 of its mate's first record).
+ * Then the fragment is n_reads += 1, records += n_records, total_mates += n_mates, unmapped_reads +=
+ * n_unmapped and (unless noop) unspliced_mates += n_mates to the ingest, and nothing else.
+ * Nothing outside [bytes, bytes + n_bytes) is read and nothing but frag_rows[0 .. first[n_blocks]) written. */
+int fc2_bam_frag_launch(const uint8_t *bytes, uint32_t n_bytes, const uint32_t *ooff, const uint32_t *isize,
+                        const uint32_t *status, const uint16_t *starts, const uint32_t *count,
+                        const fc2_bam_digest *rows, const uint32_t *first, fc2_bam_frag *frag_rows,
+                        uint32_t n_blocks, void *stream);
+/* The same rows from the same tables in host memory (the tests' oracle): `usable` is decided by
+ * fc2_bam_digest_host and the blocks' status, as fc2_bam_digest_launch decides it.  first: n_blocks + 1
+ * entries, written; frag_rows: first[n_blocks] rows (at most the sum of min(count[i], FC2_BAM_WALK_CAP)). */
+int fc2_bam_frag_host(const uint8_t *bytes, uint32_t n_bytes, const uint32_t *ooff, const uint32_t *isize,
+                      const uint32_t *status, const uint16_t *starts, const uint32_t *count,
+                      fc2_bam_frag *frag_rows, uint32_t *first, uint32_t n_blocks);
+/* Whether the parse threads step over the fragments the device closed (on = 1; needs the device lists,
+ * fc2_ingest_set_gpu_walk) or group every record themselves (0, the default).  Only where fragments are
+ * grouped on the parse threads: never with a -B writer or fc2_ingest_next's SAM text.  Holds from the
+ * next batch on.  on = 2 is a test setting for machines without a GPU: the rows of the batches the CPU
+ * inflates are filled on the host with fc2_bam_frag_host, so the same parse-thread logic runs. */
+int fc2_ingest_set_gpu_group(fc2_ingest *h, int on);
+/* Fragments the parse threads stepped over on the device's word, and every other fragment.  The pair is
+ * meant to be read once the input is exhausted: the first figure is counted by the parse threads, which
+ * run ahead of the reader, the second is the reader's n_reads less the first (0 while that is negative),
+ * so before the end the two need not add up to the fragments read so far. */
+int fc2_ingest_group_counts(const fc2_ingest *h, uint64_t *device_fragments, uint64_t *host_fragments);
 #ifdef __cplusplus
 }
 #endif
