@@ -314,6 +314,16 @@ def _gzip_device(options):
                 gzip_timeout_s=float(os.environ.get("FC2_GPU_GZIP_TIMEOUT_S") or 0))
 
 
+def _bam_device(options):
+    """spliced_alignments.bam's records compressed on the GPU (DESIGN.md §5 "BGZF output on the device"): only
+    with FC2_GPU_BAM=1, on the first of the run's devices, waiting at most FC2_GPU_BAM_TIMEOUT_S seconds (60)
+    for it.  Unset, 0 or anything else: None, zlib compresses on the reading thread."""
+    if os.environ.get("FC2_GPU_BAM") != "1":
+        return None
+    from .ctxpipe import device_index
+    return dict(mode=1, device=device_index(options.device), timeout_s=float(os.environ.get("FC2_GPU_BAM_TIMEOUT_S") or 0))
+
+
 def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory, genome, bam_path="",
                        genome_eval=None, startup=None) -> int:
     """The read loop in C++ (include/fc2_caller.h); only the breakpoint search is called from here."""
@@ -340,6 +350,7 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                               gpu_digest=_gpu_digest())
                          if genome_eval is not None else {}),
                       gpu_group=_gpu_group(),
+                      bam_device=_bam_device(options) if genome_eval is not None and bam_path else None,
                       **(_gzip_device(options) if genome_eval is not None and reads_gz else {}))
     try:
         try:
@@ -394,6 +405,8 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
             if nc.gzip_device is not None:      # the last pieces are compressed as the file is finished
                 nc.finish_reads()
             startup.update(zip(("gzip_gpu_pieces", "gzip_cpu_pieces"), nc.reads_gz_counts()))
+            if nc.bam_device:
+                startup.update(zip(("bam_gpu_pieces", "bam_cpu_pieces"), nc.bam_out_pieces))
             logger.info("process phases: " + ", ".join("%s=%.3f" % kv for kv in startup.items()) +
                         ", process_age_s=%.3f, numpy_loaded=%d, torch_loaded=%d"
                         % (process_age(), "numpy" in sys.modules, "torch" in sys.modules))

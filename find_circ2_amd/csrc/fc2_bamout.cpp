@@ -11,6 +11,9 @@
 #include <atomic>
 #include <thread>
 
+#include "../../include/fc2_caller.h"
+#include "fc2_bgzf_gpu.h"
+
 namespace fc2 {
 namespace bam {
 
@@ -78,6 +81,128 @@ struct Writer {
     bool ok = true;
     std::vector<uint8_t> out;
 
+    // the device mode (set_device): pieces [head, next) are in flight, piece p in slot p % kSlots
+    static constexpr int kSlots = bgz::kSlots;
+    static constexpr uint64_t kNever = ~0ull;
+    int mode = 0;
+    uint32_t block = 0, stride = 0;
+    size_t piece_bytes = 0;
+    bgz::Gpu *gpu = nullptr;
+    bool timed_out = false;
+    std::string dev_err;
+    std::string pend;                      // the bytes of the piece being filled
+    std::string in[kSlots];                // the bytes of the piece in slot k, for zlib if the device hands it back
+    uint64_t head = 0, next = 0;
+    uint64_t off_from = kNever;            // zlib compresses every piece from this one on
+    uint64_t gpu_pieces = 0, cpu_pieces = 0;
+    // mode 2, the host model of a slot: the tiles' streams at `stride`, their tables, the framed piece
+    struct Model {
+        std::vector<uint8_t> slots, framed;
+        std::vector<uint32_t> len, crc, off;
+        uint32_t total = 0;
+    } model[kSlots];
+
+    // what the device does with a piece, on the host: every tile raw-deflated by zlib level 1 into its slot
+    // (0xFFFFFFFF: it does not fit the slot), then fc2_bgzf_frame_host
+    bool model_submit(int k) {
+        Model &m = model[k];
+        const std::string &src = in[k];
+        const uint32_t tiles = (uint32_t)((src.size() + block - 1) / block);
+        m.slots.assign((size_t)tiles * stride, 0);
+        m.len.assign(tiles, 0);
+        m.crc.assign(tiles, 0);
+        m.off.assign(tiles + 1, 0);
+        m.framed.assign((size_t)tiles * (26 + FC2_DEFLATE_TILE_BOUND(block)), 0);
+        z_stream z1{};
+        if (deflateInit2(&z1, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        for (uint32_t i = 0; i < tiles; ++i) {
+            const size_t at = (size_t)i * block, n = std::min<size_t>(block, src.size() - at);
+            deflateReset(&z1);
+            z1.next_in = (Bytef *)(src.data() + at);
+            z1.avail_in = (uInt)n;
+            z1.next_out = m.slots.data() + (size_t)i * stride;
+            z1.avail_out = stride;
+            m.len[i] = deflate(&z1, Z_FINISH) == Z_STREAM_END ? stride - z1.avail_out : 0xFFFFFFFFu;
+            m.crc[i] = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)(src.data() + at), (uInt)n);
+        }
+        deflateEnd(&z1);
+        return fc2_bgzf_frame_host(m.slots.data(), stride, m.len.data(), m.crc.data(), tiles, src.size(), block,
+                                   m.framed.data(), m.off.data(), &m.total) == FC2_OK;
+    }
+
+    // the piece in pend into the next slot (a slot in use: its piece written first)
+    bool send_piece() {
+        if (next - head == (uint64_t)kSlots && !retire()) return false;
+        const uint64_t p = next++;
+        const int k = (int)(p % kSlots);
+        in[k].swap(pend);
+        pend.clear();
+        if (p >= off_from) return ok;
+        std::string err;
+        if (!(mode == 1 ? bgz::gpu_submit(gpu, k, in[k].data(), in[k].size(), err) : model_submit(k))) {
+            off_from = p;
+            if (mode == 1 && bgz::gpu_hung(gpu)) return fail_timeout(err);
+        }
+        return ok;
+    }
+
+    bool fail_timeout(const std::string &err) {
+        timed_out = true;
+        dev_err = err;
+        return ok = false;
+    }
+
+    // the oldest piece in flight to the file: the device's blocks, or zlib's from off_from on
+    bool retire() {
+        const uint64_t p = head++;
+        const int k = (int)(p % kSlots);
+        const uint8_t *bytes = nullptr;
+        size_t total = 0;
+        if (p < off_from) {
+            if (mode == 1) {
+                std::string err;
+                const bgz::Wait wt = bgz::gpu_collect(gpu, k, bytes, total, err);
+                if (wt == bgz::TIMED_OUT) return fail_timeout(err);
+                if (wt != bgz::DONE) total = 0;
+            } else {
+                bytes = model[k].framed.data();
+                total = model[k].total;
+            }
+            if (!total) off_from = p;           // the device failed or gave a tile up
+        }
+        if (p < off_from) {
+            if (fwrite(bytes, 1, total, fp) != total) ok = false;
+            ++gpu_pieces;
+        } else {
+            out.resize(kBlockMax);
+            for (size_t at = 0; at < in[k].size() && ok; at += block) {
+                const size_t bsize = deflate_block(zs, in[k].data() + at, std::min<size_t>(block, in[k].size() - at), out.data());
+                if (!bsize || fwrite(out.data(), 1, bsize, fp) != bsize) ok = false;
+            }
+            ++cpu_pieces;
+        }
+        in[k].clear();
+        return ok;
+    }
+
+    bool add_piece(const char *p, size_t n) {
+        while (n && ok) {
+            const size_t k = std::min(n, piece_bytes - pend.size());
+            pend.append(p, k);
+            p += k;
+            n -= k;
+            if (pend.size() == piece_bytes && !send_piece()) return false;
+        }
+        return ok;
+    }
+
+    // the rest as a last piece (its last block short), then every piece in flight, in order
+    bool drain() {
+        if (!pend.empty() && ok) send_piece();
+        while (head < next && ok) retire();
+        return ok;
+    }
+
     bool flush_block() {
         if (buf.empty()) return ok;
         out.resize(kBlockMax);
@@ -88,6 +213,7 @@ struct Writer {
         return ok;
     }
     bool add(const char *p, size_t n) {
+        if (mode) return add_piece(p, n);
         while (n) {
             const size_t k = std::min(n, kBlockIn - buf.size());
             buf.append(p, k);
@@ -134,6 +260,7 @@ bool write_raw(Writer *w, const uint8_t *rec, size_t n) { return w->add((const c
 
 bool write_bulk(Writer *w, const char *p, size_t n, int threads) {
     if (!w->ok) return false;
+    if (w->mode) return w->add(p, n);          // (the device mode cuts its own pieces)
     // the current block first (the bytes complete it or stay in it)
     const size_t head = std::min(n, kBlockIn - w->buf.size());
     w->buf.append(p, head);
@@ -295,16 +422,45 @@ bool encode_sam(const char *line, const char *end, const std::unordered_map<std:
     return true;
 }
 
-bool close_writer(Writer *w, std::string &err) {
+bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, std::string &err) {
+    if (!block) block = bgz::kDefaultBlock;
+    if (!piece_blocks) piece_blocks = bgz::kDefaultPieceBlocks;
+    if (!w || mode < 0 || mode > 2 || block > kBlockIn || piece_blocks > bgz::kMaxPieceBlocks || timeout_s < 0 ||
+        (mode == 1 && device < 0)) {
+        err = "mode is 0, 1 or 2, block at most 0xff00, piece_blocks at most 1024";
+        return false;
+    }
+    if (w->mode || !w->buf.empty()) {
+        err = "call once, before the first record";
+        return false;
+    }
+    if (!mode) return true;
+    if (mode == 1 && !(w->gpu = bgz::gpu_open(device, block, piece_blocks, timeout_s, err))) return false;
+    w->mode = mode;
+    w->block = block;
+    w->stride = (FC2_DEFLATE_TILE_BOUND(block) + 15u) & ~15u;
+    w->piece_bytes = (size_t)block * piece_blocks;
+    return true;
+}
+
+void device_counts(const Writer *w, uint64_t &gpu_pieces, uint64_t &cpu_pieces) {
+    gpu_pieces = w ? w->gpu_pieces : 0;
+    cpu_pieces = w ? w->cpu_pieces : 0;
+}
+
+bool close_writer(Writer *w, std::string &err, uint64_t *gpu_pieces, uint64_t *cpu_pieces) {
     if (!w) return true;
-    bool ok = w->flush_block();
+    bool ok = w->mode ? w->drain() : w->flush_block();
+    if (gpu_pieces) *gpu_pieces = w->gpu_pieces;
+    if (cpu_pieces) *cpu_pieces = w->cpu_pieces;
+    if (w->gpu) bgz::gpu_close(w->gpu);        // (a device that timed out is left alone)
     static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0,
                                     3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (fwrite(eof, 1, sizeof eof, w->fp) != sizeof eof) ok = false;
     if (fclose(w->fp) != 0) ok = false;
     deflateEnd(&w->zs);
+    if (!ok) err = w->timed_out ? "IOError: writing spliced_alignments.bam failed: " + w->dev_err : "IOError: writing spliced_alignments.bam failed";
     delete w;
-    if (!ok) err = "IOError: writing spliced_alignments.bam failed";
     return ok;
 }
 

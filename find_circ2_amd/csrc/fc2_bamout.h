@@ -31,8 +31,20 @@ bool encode_sam(const char *line, const char *end, const std::unordered_map<std:
 // `threads` threads and written in order; the blocks are cut where the record-by-record calls would
 // cut them, so the file is byte for byte what those calls write
 bool write_bulk(Writer *w, const char *p, size_t n, int threads);
-// flush, EOF block, close; false on an I/O error
-bool close_writer(Writer *w, std::string &err);
+// The device mode (fc2_ingest_set_bam_out_device): call after open_writer and before the first record.  The
+// record bytes are cut every `block` (1..0xff00) bytes, as the calls above cut them at 0xff00, but go out in
+// pieces of piece_blocks (1..1024) blocks: mode 1 compresses and frames a piece on GPU `device`
+// (fc2_bgzf_gpu.h), mode 2 on the host with zlib level 1 and fc2_bgzf_frame_host, through the same code
+// otherwise (a test setting); mode 0 leaves the writer as it is.  Piece p uses slot p % 4, and a slot's piece
+// is waited for and written before the slot is reused: the pieces reach the file in order, from the calling
+// thread.  A piece the device fails on or hands back, and every later one, is compressed by zlib as above.  A
+// device that does not answer within timeout_s seconds fails the call that waited and close_writer.
+bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, std::string &err);
+// pieces written from the device (or the host model), and pieces of the device mode zlib compressed, so far
+void device_counts(const Writer *w, uint64_t &gpu_pieces, uint64_t &cpu_pieces);
+// flush (the device mode: the rest as a last piece, then every piece in flight, in order), EOF block, close;
+// false on an I/O error or a device that timed out; gpu_pieces, cpu_pieces (may be null): device_counts at the end
+bool close_writer(Writer *w, std::string &err, uint64_t *gpu_pieces = nullptr, uint64_t *cpu_pieces = nullptr);
 
 }  // namespace bam
 }  // namespace fc2

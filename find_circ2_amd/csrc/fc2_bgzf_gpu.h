@@ -1,0 +1,44 @@
+// fc2_bgzf_gpu.h -- the host side of BGZF output compressed on the GPU (fc2_bgzf_out.hip), for
+// spliced_alignments.bam's device mode (fc2_bamout.cpp) and fc2_gpu_bgzf: a piece of up to piece_blocks
+// blocks goes up to the device, deflate_kernel (fc2_deflate.hip) turns every block's input into a raw
+// DEFLATE stream in a slot of its own, bgzf_frame_kernel packs the slots into the finished block stream,
+// and only that stream's `total` bytes come back.  The same slot discipline as the gzip writer's
+// (fc2_deflate_gpu.h): four slots, each with its own stream, device and pinned buffers, made once and
+// reused; no wait on the device is unbounded, and a device that did not answer in time is not touched
+// again.  Used from one thread at a time.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+
+namespace fc2 {
+namespace bgz {
+
+struct Gpu;
+constexpr int kSlots = 4;                      // pieces in flight
+constexpr uint32_t kDefaultBlock = 0xff00;     // the CPU writer's cut (htslib's BGZF_BLOCK_SIZE)
+constexpr uint32_t kDefaultPieceBlocks = 64;
+constexpr uint32_t kMaxPieceBlocks = 1024;
+constexpr double kDefaultTimeout = 60.0;       // seconds a wait for the device may take
+
+// pieces of at most piece_blocks (1..kMaxPieceBlocks) blocks of `block` (1..0xff00) input bytes, every wait
+// for the device at most timeout_s seconds (<= 0: kDefaultTimeout); nullptr and err on failure
+Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, std::string &err);
+// frees everything; a device that timed out is not waited for (its buffers are left to the process's end)
+void gpu_close(Gpu *g);
+// a wait timed out: the device is not touched again, every later call fails
+bool gpu_hung(const Gpu *g);
+
+// n bytes (1..block * piece_blocks) into the idle slot: copied to its pinned buffer, then the upload, both
+// kernels and the download of the piece's total queued on its stream.  False (and err) if something failed:
+// the slot stays idle
+bool gpu_submit(Gpu *g, int slot, const char *data, size_t n, std::string &err);
+enum Wait { DONE = 0, FAILED = 1, TIMED_OUT = 2 };
+// waits for the slot's piece (at most timeout_s seconds), then downloads exactly its `total` bytes and waits
+// for them in the same way; the slot is idle afterwards.  After DONE: the piece's blocks at bytes, total of
+// them, valid until the slot's next gpu_submit -- total 0: a tile was given up, the caller compresses the piece
+Wait gpu_collect(Gpu *g, int slot, const uint8_t *&bytes, size_t &total, std::string &err);
+
+}  // namespace bgz
+}  // namespace fc2

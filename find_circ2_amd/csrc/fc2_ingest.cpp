@@ -640,6 +640,7 @@ struct fc2_ingest {
     fc2::bam::Writer *bam_out = nullptr;
     bool bam_stopped = false;    // the reference raised inside process_mate: nothing after it is written
     std::string bam_err;
+    uint64_t bam_gpu_pieces = 0, bam_cpu_pieces = 0;    // fc2_ingest_bam_out_counts, once the writer is closed
     // grouping state
     bool started = false;
     Mate current, other;
@@ -2391,10 +2392,34 @@ extern "C" int fc2_ingest_set_bam_out(fc2_ingest *h, const char *path) {
     return h->bam_out ? FC2_OK : fc2::fail(FC2_E_IO, err);
 }
 
+extern "C" int fc2_ingest_set_bam_out_device(fc2_ingest *h, int mode, int device, uint32_t block, uint32_t piece_blocks,
+                                             double timeout_s) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: null argument");
+    if (!h->bam_out || h->n_records)
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: call after fc2_ingest_set_bam_out, before reading");
+    if (mode < 0 || mode > 2 || block > 0xff00 || piece_blocks > 1024 || timeout_s < 0 || (mode == 1 && device < 0))
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: mode is 0, 1 or 2, block at most 0xff00, "
+                                      "piece_blocks at most 1024");
+    std::string err;
+    if (!fc2::bam::set_device(h->bam_out, mode, device, block, piece_blocks, timeout_s, err))
+        return fc2::fail(mode == 1 ? FC2_E_HIP : FC2_E_PARAM, "fc2_ingest_set_bam_out_device: " + err);
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_bam_out_counts(const fc2_ingest *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_bam_out_counts: null argument");
+    // (they outlive fc2_ingest_close_bam_out, which writes the last pieces)
+    uint64_t g = h->bam_gpu_pieces, c = h->bam_cpu_pieces;
+    if (h->bam_out) fc2::bam::device_counts(h->bam_out, g, c);
+    if (gpu_pieces) *gpu_pieces = g;
+    if (cpu_pieces) *cpu_pieces = c;
+    return FC2_OK;
+}
+
 extern "C" int fc2_ingest_close_bam_out(fc2_ingest *h) {
     if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_close_bam_out: null argument");
     std::string err;
-    const bool ok = fc2::bam::close_writer(h->bam_out, err);
+    const bool ok = fc2::bam::close_writer(h->bam_out, err, &h->bam_gpu_pieces, &h->bam_cpu_pieces);
     h->bam_out = nullptr;
     return ok ? FC2_OK : fc2::fail(FC2_E_IO, err);
 }

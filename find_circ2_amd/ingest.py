@@ -49,9 +49,19 @@ class NativeIngest:
                 frags.append([parse_sam_line(l, self.tid_of) for l in block.split("\n") if l])
         return frags
 
-    def set_bam_out(self, path: str):
-        """-B/--bam: anchor alignments to ``path`` (include/fc2_ingest.h)."""
+    def set_bam_out(self, path: str, bam_device=None):
+        """-B/--bam: anchor alignments to ``path`` (include/fc2_ingest.h).  bam_device: None, or the
+        arguments of fc2_ingest_set_bam_out_device as a dict -- mode (1: the records compressed on GPU
+        ``device``; 2: by the host model of it, a test setting), device, block, piece_blocks, timeout_s
+        (each 0 or absent: the default)."""
         N.check(N.lib().fc2_ingest_set_bam_out(self.h, path.encode()))
+        if bam_device:
+            set_bam_out_device(self.h, bam_device)
+
+    def bam_out_counts(self) -> Tuple[int, int]:
+        """(pieces of spliced_alignments.bam the device compressed, pieces of the device mode zlib
+        compressed); final after close_bam_out, (0, 0) without bam_device."""
+        return bam_out_counts(self.h)
 
     def set_gpu_inflate(self, device: int, wait: bool = True):
         """A BGZF input's blocks inflated on GPU ``device`` from the next batch on (include/fc2_ingest.h);
@@ -121,6 +131,19 @@ class NativeIngest:
             self.close()
         except Exception:
             pass
+
+
+def set_bam_out_device(h, bam_device) -> None:
+    """fc2_ingest_set_bam_out_device on the ingest handle ``h`` (NativeIngest.set_bam_out's bam_device)."""
+    d = dict(bam_device)
+    N.check(N.lib().fc2_ingest_set_bam_out_device(h, int(d.get("mode", 1)), int(d.get("device", 0)), int(d.get("block", 0)),
+                                                  int(d.get("piece_blocks", 0)), float(d.get("timeout_s", 0.0))))
+
+
+def bam_out_counts(h) -> Tuple[int, int]:
+    g, c = ctypes.c_uint64(), ctypes.c_uint64()
+    N.check(N.lib().fc2_ingest_bam_out_counts(h, ctypes.byref(g), ctypes.byref(c)))
+    return int(g.value), int(c.value)
 
 
 def sam_to_bam(sam_path: str, bam_path: str) -> None:

@@ -74,7 +74,7 @@ class NativeCaller:
                  write_multi=True, genome_dummy=False, known_circ: str = "", known_lin: str = "",
                  bam_out: str = "", reads_gz=None, inflate_device=None, inflate_after: int = 0,
                  gzip_device=None, gzip_tile: int = 0, gzip_timeout_s: float = 0.0, gpu_walk: bool = True,
-                 gpu_digest: bool = False, gpu_group: int = 0):
+                 gpu_digest: bool = False, gpu_group: int = 0, bam_device=None):
         o = copts
         # the strings must outlive the handle's open call (fc2_caller_open copies them)
         self._keep = [o.name.encode(), known_circ.encode() if known_circ else None,
@@ -92,7 +92,9 @@ class NativeCaller:
         self._path = path
         self._is_bam = is_bam
         self.bam_out = bam_out
-        self.reads_gz = reads_gz     # (path, level, threads, piece): spliced_reads.fastq.gz written natively
+        self.bam_device = bam_device   # spliced_alignments.bam's records compressed on a GPU (ingest.set_bam_out_device's dict)
+        self.bam_out_pieces = (0, 0)   # ... (pieces from the device, pieces zlib compressed), once close_bam_out ran
+        self.reads_gz = reads_gz    # (path, level, threads, piece): spliced_reads.fastq.gz written natively
         self.inflate_device = inflate_device   # a BGZF input's blocks inflated on this GPU (None: the CPU)
         self.inflate_after = inflate_after     # ... once this many bytes of the input were read
         self.gpu_walk = gpu_walk               # ... their BAM record starts listed there too (else by host threads)
@@ -117,6 +119,9 @@ class NativeCaller:
         self.format = "bam" if L.fc2_ingest_format(ing, None) == 1 else "sam"      # FC2_INGEST_BAM
         if self.bam_out:
             N.check(L.fc2_ingest_set_bam_out(ing, self.bam_out.encode()))
+            if self.bam_device:
+                from .ingest import set_bam_out_device
+                set_bam_out_device(ing, self.bam_device)
         if self.inflate_device is not None:
             N.check(L.fc2_ingest_set_gpu_inflate_from(ing, int(self.inflate_device), int(self.inflate_after)))
             N.check(L.fc2_ingest_set_gpu_walk(ing, int(bool(self.gpu_walk))))
@@ -146,7 +151,11 @@ class NativeCaller:
     def close_bam_out(self):
         """Finish spliced_alignments.bam (EOF block); raises on a write error."""
         if self.bam_out:
-            N.check(N.lib().fc2_ingest_close_bam_out(N.lib().fc2_caller_ingest(self.h)))
+            ing = N.lib().fc2_caller_ingest(self.h)
+            N.check(N.lib().fc2_ingest_close_bam_out(ing))
+            if self.bam_device:
+                from .ingest import bam_out_counts
+                self.bam_out_pieces = bam_out_counts(ing)
 
     def inflate_counts(self):
         """(BGZF blocks inflated on the GPU, on the CPU) since the GPU inflate was set (0, 0 without)."""

@@ -147,6 +147,30 @@ uint64_t fc2_deflate_scratch_bytes(uint64_t n_bytes, uint32_t tile);
 int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, void *out, uint64_t cap, uint64_t *out_n);
 uint64_t fc2_gpu_gzip_bound(uint64_t n, uint32_t tile);
 
+/* ---- BGZF output on the GPU (csrc/fc2_bgzf_out.hip; the rule: csrc/fc2_bgzf_frame_impl.h) ---- */
+/* The slots fc2_deflate_launch filled (n_tiles tiles of `tile` input bytes, 1..0xff00, the last one holding the
+ * rest of n_bytes; slots and stride multiples of 16) packed into BGZF blocks on `stream`: block i -- the 18
+ * header bytes with BSIZE - 1, tile i's out_len[i] stream bytes, crc[i], ISIZE -- at out + off[i], off[i] =
+ * the sum over j < i of 26 + out_len[j]; off[n_tiles] = *total.  out holds n_tiles * (26 +
+ * FC2_DEFLATE_TILE_BOUND(tile)) bytes; nothing outside [out, out + *total) is written.  A tile whose out_len is
+ * 0xFFFFFFFF, 0 or above the bound makes the piece unwritten: *total = 0, every offset 0.  FC2_E_PARAM (nothing
+ * launched) for a tile outside 1..0xff00, more than 65535 tiles, or n_bytes that does not end in the last tile.
+ * All pointers are device memory. */
+int fc2_bgzf_frame_launch(const uint8_t *slots, uint32_t stride, const uint32_t *out_len, const uint32_t *crc,
+                          uint32_t n_tiles, uint64_t n_bytes, uint32_t tile, uint8_t *out, uint32_t *off,
+                          uint32_t *total, void *stream);
+/* the same rule on host memory (slots at any alignment); *total = 0 also when the arguments are refused */
+int fc2_bgzf_frame_host(const uint8_t *slots, uint32_t stride, const uint32_t *out_len, const uint32_t *crc,
+                        uint32_t n_tiles, uint64_t n_bytes, uint32_t tile, uint8_t *out, uint32_t *off,
+                        uint32_t *total);
+/* one buffer through the device writer of spliced_alignments.bam (csrc/fc2_bgzf_gpu.h), for tests and other
+ * hosts: in[0, n) as BGZF blocks of `block` (1..0xff00) input bytes, in pieces of piece_blocks (0: 64; at most
+ * 1024) blocks, four in flight, into out (cap bytes); no EOF block, and nothing for n = 0.  FC2_E_RANGE if the
+ * blocks do not fit, FC2_E_PARAM for a block outside 1..0xff00. */
+int fc2_gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, void *out,
+                 uint64_t cap, uint64_t *out_n);
+uint64_t fc2_gpu_bgzf_bound(uint64_t n, uint32_t block);
+
 /* The BED rows (no header) of 0 = circ_splice_sites.bed, 1 = lin_splice_sites.bed
  * (call once, at the end).  Once the input was read to its end and every chunk submitted, the first
  * call releases the read side -- the input (so finish -B output with fc2_ingest_close_bam_out

@@ -81,6 +81,24 @@ int fc2_ingest_counts_get(const fc2_ingest *h, fc2_ingest_counts *counts);
  * finished (EOF block) by fc2_ingest_close_bam_out or fc2_ingest_close. */
 int fc2_ingest_set_bam_out(fc2_ingest *h, const char *path);
 int fc2_ingest_close_bam_out(fc2_ingest *h);
+/* The records of spliced_alignments.bam compressed on a GPU instead of by zlib on the calling thread: call
+ * after fc2_ingest_set_bam_out and before the first fc2_ingest_next.  mode 0: off (the default); 1: GPU
+ * `device` (fc2_deflate_launch at tile = block, then fc2_bgzf_frame_launch, include/fc2_caller.h); 2: the
+ * host model of the device -- every tile raw-deflated by zlib level 1 and framed by fc2_bgzf_frame_host,
+ * through the same writer code otherwise (a test setting).  The header block(s) stay zlib's.  The record bytes
+ * are cut every `block` bytes (0: 0xff00, where the zlib writer cuts them; at most 0xff00), so the file's
+ * ISIZE values are those of mode 0 and only the compressed payloads differ.  piece_blocks (0: 64; at most
+ * 1024) blocks make a piece; piece p uses slot p % 4, and a slot's piece is waited for and written before the
+ * slot is reused: pieces are written in order, by the calling thread.  fc2_ingest_close_bam_out sends the rest
+ * as a last piece, writes every piece in flight and the EOF block.  If the device fails or hands a piece back,
+ * zlib compresses that piece and every later one.  A device that does not answer within timeout_s (0: 60)
+ * seconds fails the call that waited, and fc2_ingest_close_bam_out, with FC2_E_IO; it is not touched again.
+ * At the defaults the four slots hold 31.9 MiB of pinned host and 111.6 MiB of device memory. */
+int fc2_ingest_set_bam_out_device(fc2_ingest *h, int mode, int device, uint32_t block, uint32_t piece_blocks,
+                                  double timeout_s);
+/* pieces the device (mode 2: its host model) compressed, and pieces of the device mode zlib compressed, so
+ * far; final after fc2_ingest_close_bam_out (0, 0 without the device mode) */
+int fc2_ingest_bam_out_counts(const fc2_ingest *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces);
 
 /* ``samtools view -b`` for SAM text (any compression): every record encoded as htslib's
  * sam_parse1 does (the -B encoder above), BGZF blocks (zlib level 1, as samtools view -1) + EOF block.  Used to make BAM inputs for

@@ -19,9 +19,10 @@ With --check the largest size also runs through the Python read loop (--python-c
 search) and every output file must be byte-identical.  One JSON line on stdout; progress on stderr.
 
 usage: python scripts/cli_steady.py [--sizes 2000000,20000000] [--threads 4,8,16,32] [--reps 1]
-                                    [--check] [--out DIR] [--keep] [--sites K] [--variants K=V,...]
+                                    [--check] [--out DIR] [--keep] [--sites K] [--variants K=V,...] [-B]
 --sites K: the spliced reads cross K planted junctions (many reads per junction, as in a real
 library) instead of one junction each (the junction tables then stay small).
+-B: every run writes spliced_alignments.bam too (the CLI's -B; --variants FC2_GPU_BAM=1 compresses it on the GPU).
 Each run's record is printed as its own JSON line as soon as it is done; the summary comes last.
 """
 import argparse
@@ -212,7 +213,9 @@ def main():
                          "(e.g. FC2_GPU_INFLATE=0)")
     ap.add_argument("--sites", type=int, default=0,
                     help="junction sites the spliced reads cross (scripts/gen_reads.c); 0: one per read")
+    ap.add_argument("-B", "--bam", action="store_true", help="run the CLI with -B (spliced_alignments.bam)")
     a = ap.parse_args()
+    extra = ["-B"] if a.bam else []
     sizes = [int(x) for x in a.sizes.split(",")]
     threads = [int(x) for x in a.threads.split(",") if x.strip() and x != "none"]
     import tempfile
@@ -234,7 +237,7 @@ def main():
                 # accounting (it also closes the caller at exit to print the totals)
                 for r in list(range(a.reps)) + ["timing"]:
                     out = os.path.join(d, "o_%d_%d_%s%s" % (n, t, r, "_" + var.replace("=", "") if var else ""))
-                    x = run_cli(fa, bams[n], out, t, timing=(r == "timing"),
+                    x = run_cli(fa, bams[n], out, t, extra=extra, timing=(r == "timing"),
                                 env_extra=dict([var.split("=", 1)]) if var else None)
                     x["size"] = n
                     x["rep"] = r
