@@ -306,22 +306,26 @@ def _gpu_group():
 def _gzip_device(options):
     """spliced_reads.fastq.gz compressed on the GPU: only with FC2_GPU_GZIP=1, on the first of
     the run's devices, in tiles of FC2_GPU_GZIP_TILE bytes (32768), waiting at most
-    FC2_GPU_GZIP_TIMEOUT_S seconds (60) for the device.  Anything but 1: {}, the worker threads compress."""
+    FC2_GPU_GZIP_TIMEOUT_S seconds (60) for the device, at the compressor's level 2 with FC2_GPU_GZIP_LEVEL=2
+    (unset or anything else: level 1).  Anything but 1: {}, the worker threads compress."""
     if os.environ.get("FC2_GPU_GZIP") != "1":
         return {}
     from .ctxpipe import device_index
     return dict(gzip_device=device_index(options.device), gzip_tile=int(os.environ.get("FC2_GPU_GZIP_TILE") or 0),
-                gzip_timeout_s=float(os.environ.get("FC2_GPU_GZIP_TIMEOUT_S") or 0))
+                gzip_timeout_s=float(os.environ.get("FC2_GPU_GZIP_TIMEOUT_S") or 0),
+                gzip_level=2 if os.environ.get("FC2_GPU_GZIP_LEVEL") == "2" else 1)
 
 
 def _bam_device(options):
     """spliced_alignments.bam's records compressed on the GPU (DESIGN.md §5 "BGZF output on the device"): only
     with FC2_GPU_BAM=1, on the first of the run's devices, waiting at most FC2_GPU_BAM_TIMEOUT_S seconds (60)
-    for it.  Unset, 0 or anything else: None, zlib compresses on the reading thread."""
+    for it, at the compressor's level 2 with FC2_GPU_BAM_LEVEL=2 (unset or anything else: level 1).  Unset, 0
+    or anything else: None, zlib compresses on the reading thread."""
     if os.environ.get("FC2_GPU_BAM") != "1":
         return None
     from .ctxpipe import device_index
-    return dict(mode=1, device=device_index(options.device), timeout_s=float(os.environ.get("FC2_GPU_BAM_TIMEOUT_S") or 0))
+    return dict(mode=1, device=device_index(options.device), timeout_s=float(os.environ.get("FC2_GPU_BAM_TIMEOUT_S") or 0),
+                level=2 if os.environ.get("FC2_GPU_BAM_LEVEL") == "2" else 1)
 
 
 def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory, genome, bam_path="",
@@ -407,7 +411,9 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
             startup.update(zip(("gzip_gpu_pieces", "gzip_cpu_pieces"), nc.reads_gz_counts()))
             if nc.bam_device:
                 startup.update(zip(("bam_gpu_pieces", "bam_cpu_pieces"), nc.bam_out_pieces))
-            logger.info("process phases: " + ", ".join("%s=%.3f" % kv for kv in startup.items()) +
+            levels = (", gzip_gpu_level=2" if nc.gzip_device is not None and nc.gzip_level == 2 else "") + \
+                (", bam_gpu_level=2" if nc.bam_device and nc.bam_device.get("level") == 2 else "")
+            logger.info("process phases: " + ", ".join("%s=%.3f" % kv for kv in startup.items()) + levels +
                         ", process_age_s=%.3f, numpy_loaded=%d, torch_loaded=%d"
                         % (process_age(), "numpy" in sys.modules, "torch" in sys.modules))
     finally:

@@ -422,7 +422,10 @@ bool encode_sam(const char *line, const char *end, const std::unordered_map<std:
     return true;
 }
 
-bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, std::string &err) {
+bool device_set(const Writer *w) { return w && w->mode != 0; }
+
+bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level,
+                std::string &err) {
     if (!block) block = bgz::kDefaultBlock;
     if (!piece_blocks) piece_blocks = bgz::kDefaultPieceBlocks;
     if (!w || mode < 0 || mode > 2 || block > kBlockIn || piece_blocks > bgz::kMaxPieceBlocks || timeout_s < 0 ||
@@ -435,7 +438,7 @@ bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_
         return false;
     }
     if (!mode) return true;
-    if (mode == 1 && !(w->gpu = bgz::gpu_open(device, block, piece_blocks, timeout_s, err))) return false;
+    if (mode == 1 && !(w->gpu = bgz::gpu_open(device, block, piece_blocks, timeout_s, level, err))) return false;
     w->mode = mode;
     w->block = block;
     w->stride = (FC2_DEFLATE_TILE_BOUND(block) + 15u) & ~15u;

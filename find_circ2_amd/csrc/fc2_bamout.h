@@ -39,7 +39,9 @@ bool write_bulk(Writer *w, const char *p, size_t n, int threads);
 // is waited for and written before the slot is reused: the pieces reach the file in order, from the calling
 // thread.  A piece the device fails on or hands back, and every later one, is compressed by zlib as above.  A
 // device that does not answer within timeout_s seconds fails the call that waited and close_writer.
-bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, std::string &err);
+bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level,
+                std::string &err);
+bool device_set(const Writer *w);              // set_device has put the writer into mode 1 or 2
 // pieces written from the device (or the host model), and pieces of the device mode zlib compressed, so far
 void device_counts(const Writer *w, uint64_t &gpu_pieces, uint64_t &cpu_pieces);
 // flush (the device mode: the rest as a last piece, then every piece in flight, in order), EOF block, close;

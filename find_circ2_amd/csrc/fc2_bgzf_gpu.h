@@ -23,8 +23,9 @@ constexpr uint32_t kMaxPieceBlocks = 1024;
 constexpr double kDefaultTimeout = 60.0;       // seconds a wait for the device may take
 
 // pieces of at most piece_blocks (1..kMaxPieceBlocks) blocks of `block` (1..0xff00) input bytes, every wait
-// for the device at most timeout_s seconds (<= 0: kDefaultTimeout); nullptr and err on failure
-Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, std::string &err);
+// for the device at most timeout_s seconds (<= 0: kDefaultTimeout), compressed at `level` (1 or 2:
+// fc2_deflate_launch_level); nullptr and err on failure
+Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level, std::string &err);
 // frees everything; a device that timed out is not waited for (its buffers are left to the process's end)
 void gpu_close(Gpu *g);
 // a wait timed out: the device is not touched again, every later call fails

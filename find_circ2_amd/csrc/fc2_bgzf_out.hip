@@ -177,6 +177,7 @@ struct Gpu {
     uint32_t block = kDefaultBlock, stride = 0, max_tiles = 0;
     size_t max_piece = 0, out_cap = 0;
     double timeout_s = kDefaultTimeout;
+    int level = 1;                             // fc2_deflate_launch_level's
     bool hung = false;                         // a wait timed out: the device is not touched again
     Slot slot[kSlots];
 };
@@ -210,9 +211,10 @@ static Wait wait_event(Gpu *g, Slot &s, std::string &err) {
     }
 }
 
-Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, std::string &err) {
-    if (!block || block > bgzf::kTileMax || !piece_blocks || piece_blocks > kMaxPieceBlocks || device < 0) {
-        err = "GPU BGZF: bad block size, piece size or device";
+Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level, std::string &err) {
+    if (!block || block > bgzf::kTileMax || !piece_blocks || piece_blocks > kMaxPieceBlocks || device < 0 || level < 1 ||
+        level > 2) {
+        err = "GPU BGZF: bad block size, piece size, device or level";
         return nullptr;
     }
     Gpu *g = new Gpu();
@@ -223,6 +225,7 @@ Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_
     g->max_piece = (size_t)block * piece_blocks;
     g->out_cap = (size_t)piece_blocks * (bgzf::kOverhead + FC2_DEFLATE_TILE_BOUND(block));
     g->timeout_s = timeout_s > 0 ? timeout_s : kDefaultTimeout;
+    g->level = level;
     const size_t slots = (size_t)g->max_tiles * g->stride, meta = ((size_t)g->max_tiles * 3 + 2) * sizeof(uint32_t),
                  scratch = (size_t)fc2_deflate_scratch_bytes(g->max_piece, block);
     bool ok = hip_ok(hipSetDevice(device), "hipSetDevice", err);
@@ -294,7 +297,8 @@ bool gpu_submit(Gpu *g, int k, const char *data, size_t n, std::string &err) {
     s.busy = true;
     const bool ok =
         hip_ok(hipMemcpyAsync(s.d_src, s.h_src, n, hipMemcpyHostToDevice, s.stream), "upload", err) &&
-        (fc2_deflate_launch(s.d_src, n, g->block, s.d_slots, g->stride, d_len, d_crc, s.d_scratch, s.stream) == FC2_OK ||
+        (fc2_deflate_launch_level(s.d_src, n, g->block, s.d_slots, g->stride, d_len, d_crc, s.d_scratch, s.stream, g->level) ==
+             FC2_OK ||
          ((err = "GPU BGZF: the compressor's launch failed"), false)) &&
         (fc2_bgzf_frame_launch(s.d_slots, g->stride, d_len, d_crc, s.tiles, n, g->block, s.d_out, d_off, d_total, s.stream) ==
              FC2_OK || ((err = "GPU BGZF: the framing launch failed"), false)) &&
@@ -400,14 +404,20 @@ extern "C" uint64_t fc2_gpu_bgzf_bound(uint64_t n, uint32_t block) {
 
 extern "C" int fc2_gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, void *out,
                             uint64_t cap, uint64_t *out_n) {
+    return fc2_gpu_bgzf_level(device, in, n, block, piece_blocks, 1, out, cap, out_n);
+}
+
+extern "C" int fc2_gpu_bgzf_level(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, int level,
+                                  void *out, uint64_t cap, uint64_t *out_n) {
     using namespace fc2;
-    if (!block || block > kTileMax || piece_blocks > bgz::kMaxPieceBlocks || device < 0 || !out || !out_n || (!in && n))
+    if (!block || block > kTileMax || piece_blocks > bgz::kMaxPieceBlocks || device < 0 || !out || !out_n || (!in && n) ||
+        level < 1 || level > 2)
         return fc2::fail(FC2_E_PARAM, "fc2_gpu_bgzf: bad arguments (block is 1..0xff00, piece_blocks at most 1024)");
     *out_n = 0;
     if (!n) return FC2_OK;
     if (!piece_blocks) piece_blocks = bgz::kDefaultPieceBlocks;
     std::string err;
-    bgz::Gpu *g = bgz::gpu_open(device, block, piece_blocks, 0, err);
+    bgz::Gpu *g = bgz::gpu_open(device, block, piece_blocks, 0, level, err);
     if (!g) return fc2::fail(FC2_E_HIP, "fc2_gpu_bgzf: " + err);
     const char *src = static_cast<const char *>(in);
     uint8_t *o = static_cast<uint8_t *>(out);

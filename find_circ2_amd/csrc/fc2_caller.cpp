@@ -888,6 +888,7 @@ struct fc2_caller {
     bool submitted = false;                     // fc2_caller_submit was called (fc2_caller_set_reads_gz_device: before)
     uint32_t gz_tile = 0;                       // fc2_caller_set_reads_gz_device_tuning (0: the defaults)
     double gz_timeout_s = 0;
+    int gz_level = 1;                           // fc2_caller_set_reads_gz_device_level
     uint64_t n_chunks = 0;                      // chunks formed (next side)
 };
 
@@ -2703,7 +2704,7 @@ extern "C" int fc2_caller_set_reads_gz_device(fc2_caller *h, int device) {
         return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: call once, after fc2_caller_set_reads_gz and before "
                                       "the first fc2_caller_submit");
     std::string err;
-    if (!h->reads_gz.set_device(device, h->gz_tile, h->gz_timeout_s, err)) return fc2::fail(FC2_E_HIP, "fc2_caller_set_reads_gz_device: " + err);
+    if (!h->reads_gz.set_device(device, h->gz_tile, h->gz_timeout_s, h->gz_level, err)) return fc2::fail(FC2_E_HIP, "fc2_caller_set_reads_gz_device: " + err);
     return FC2_OK;
 }
 
@@ -2714,6 +2715,15 @@ extern "C" int fc2_caller_set_reads_gz_device_tuning(fc2_caller *h, uint32_t til
         return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_tuning: call before fc2_caller_set_reads_gz_device");
     h->gz_tile = tile;
     h->gz_timeout_s = timeout_s;
+    return FC2_OK;
+}
+
+extern "C" int fc2_caller_set_reads_gz_device_level(fc2_caller *h, int level) {
+    if (!h || level < 1 || level > 2)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_level: null handle, or a level that is not 1 or 2");
+    if (h->reads_gz.device_mode())
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_level: call before fc2_caller_set_reads_gz_device");
+    h->gz_level = level;
     return FC2_OK;
 }
 

@@ -25,6 +25,34 @@
 //
 // LDS: 22540 B beside the tile (hash table 16 KiB, staging 3 KiB, histograms, codes): 55324 B with a
 // tile of 32 KiB -- two workgroups a CU of 160 KiB -- and 88092 B with one of 64 KiB: one a CU.
+//
+// Level 2 (deflate_kernel<2>, fc2_deflate_launch_level) is the same kernel with a deeper pass 1; what
+// follows pass 1 is shared, and level 1's instantiation has neither the code nor the LDS below.
+//   Links.  Beside the table of heads there is link[], one 16-bit entry per position, indexed by
+// p & 32767: the distance from p back to the head its step read for it before the step's own positions
+// were entered (1..32768), or 0 for none -- no head, or one more than 32768 back.  Every position with
+// p + 4 <= n writes its entry where it enters itself into the heads; the 64 positions of a step have 64
+// slots of their own, so link[], like the heads, does not depend on the order of the lanes.
+//   Search.  A position p >= skip walks at most 8 candidates: the head it read, then
+// c - link[c & 32767] (so every candidate lies strictly below the one before).  The walk ends before a
+// candidate that is none, that is more than 32768 back, or whose link slot this very step has
+// rewritten (c + 32768 < base + 64: position c + 32768 is one of the step's own).  A candidate whose
+// first four bytes are p's gets its length as at level 1, at most min(n - p, 258); the longest is kept,
+// the first found (the nearest) among equal ones; once the kept length reaches 32 or the cap the walk
+// ends.  The kept match must pass level 1's cost rule.
+//   Lazy resolution.  Going up from the lowest open position of the step: the match at step index i is
+// dropped for a literal if i + 1 < 64 and index i + 1 found a longer one; else it is taken as at level
+// 1.  Nothing is deferred from index 63 to the next step.
+//   Bounds (link[]).  link[] has min(tile rounded up to 4, 32768) entries behind the tile's padding.  A
+// store is at p & 32767 with p < n <= tile; a load at c & 32767 with c < p, since the first candidate
+// is a head of an earlier step and every further one is c - back with 1 <= back <= c, checked before
+// the subtraction.  Every c walked is a position that entered itself and so wrote its entry: no entry
+// is read before it is written, and the slot of c cannot hold c + 32768's entry, because the walk has
+// ended where c + 32768 < base + 64 and later positions have not been entered yet.  The walk is bounded
+// by 8 and by the falling candidate, the extension by 258; tile bytes are read up to c + 258 + 3 <
+// n + 16, as at level 1.  Level 2 adds no store to global memory.
+//   LDS at level 2: 2 bytes more per position of the window: 120860 B with a tile of 32 KiB, 153372 B
+// at 0xff00, 153628 B at 64 KiB -- one workgroup a CU at every tile over some 19 KiB.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -41,6 +69,9 @@ namespace {
 constexpr uint32_t kTileMax = 65536;
 constexpr int kHashBits = 12;
 constexpr uint32_t kMinMatch = 4, kMaxMatch = 258, kMaxDist = 32768;
+constexpr uint32_t kLinks = 32768;             // level 2: link[] slots (a power of two: the window)
+constexpr int kDepth = 8;                      // level 2: candidates a position walks at most
+constexpr uint32_t kNice = 32;                 // level 2: a kept length that ends the walk
 constexpr uint32_t kStageWords = 768;          // 3 KiB: flushed once 2 KiB are full; a step adds < 400 bytes
 constexpr uint32_t kStageFlush = 2048;
 constexpr uint32_t kTokMatch = 0x80000000u;    // token: a literal's byte, or this | (len - 3) << 16 | (dist - 1)
@@ -258,6 +289,7 @@ __device__ __forceinline__ void put(Lds &L, Out &o, uint32_t v, uint32_t nb) {
     o.bit += nb;
 }
 
+template <int kLevel>
 __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__ src, uint64_t n_bytes, uint32_t tile,
                                                      uint8_t *__restrict__ dst, uint32_t stride,
                                                      uint32_t *__restrict__ out_len, uint32_t *__restrict__ crc,
@@ -265,6 +297,8 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     extern __shared__ __align__(16) uint8_t smem[];
     Lds &L = *reinterpret_cast<Lds *>(smem);
     uint32_t *T = L.tile;
+    uint16_t *link = nullptr;                  // level 2's links, behind the tile and its 16 bytes of padding (lds_bytes)
+    if constexpr (kLevel == 2) link = reinterpret_cast<uint16_t *>(smem + offsetof(Lds, tile) + ((tile + 3u) & ~3u) + 16u);
     const uint32_t blk = blockIdx.x;
     const int lane = (int)threadIdx.x;
     const uint64_t start = (uint64_t)blk * tile;
@@ -358,10 +392,49 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
         const uint32_t cand = can ? L.htab[h] : 0u;
         __syncthreads();
         if (can) atomicMax(&L.htab[h], p + 1u);
+        if constexpr (kLevel == 2) {
+            if (can) link[p & (kLinks - 1u)] = (uint16_t)(cand && p + 1u - cand <= kMaxDist ? p + 1u - cand : 0u);
+        }
         __syncthreads();
         if (skip >= base + 64u) continue;       // (uniform) the whole step lies inside a match
         uint32_t mlen = 0, mdist = 0;
-        if (cand && p >= skip) {
+        if constexpr (kLevel == 2) {
+            if (cand && p >= skip) {
+                const uint32_t maxlen = n - p < kMaxMatch ? n - p : kMaxMatch;
+                uint32_t c = cand - 1u, best = 0, bestd = 0;
+                for (int k = 0; k < kDepth; ++k) {
+                    const uint32_t d = p - c;
+                    if (d > kMaxDist || c + kLinks < base + 64u) break;
+                    if (load32u(T, c) == v) {
+                        uint32_t l = 4;
+                        while (l < maxlen) {
+                            const uint32_t x = load32u(T, c + l) ^ load32u(T, p + l);
+                            if (x) {
+                                l += (uint32_t)(__ffs((int)x) - 1) >> 3;
+                                break;
+                            }
+                            l += 4;
+                        }
+                        l = l < maxlen ? l : maxlen;
+                        if (l > best) {
+                            best = l;
+                            bestd = d;
+                        }
+                        if (best >= kNice || best >= maxlen) break;
+                    }
+                    const uint32_t back = link[c & (kLinks - 1u)];
+                    if (!back || back > c) break;   // (back <= c: it points at a position of the tile)
+                    c -= back;
+                }
+                if (best) {
+                    const uint32_t deb = bestd > 4u ? 30u - (uint32_t)__clz((int)(bestd - 1u)) : 0u;
+                    if (best * lit16 >= 16u * (11u + deb)) {
+                        mlen = best;
+                        mdist = bestd;
+                    }
+                }
+            }
+        } else if (cand && p >= skip) {
             const uint32_t c = cand - 1u;       // < p: positions of earlier steps only
             const uint32_t d = p - c;
             if (d <= kMaxDist && load32u(T, c) == v) {
@@ -394,6 +467,13 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
             if (!mm) break;
             const uint32_t l = (uint32_t)__ffsll((long long)mm) - 1u;
             const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)l);
+            if constexpr (kLevel == 2) {        // a longer match one position on: this one is a literal
+                if (l + 1u < 64u && ((found >> (l + 1u)) & 1ull) &&
+                    (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)((l + 1u) & 63u)) > len) {
+                    cur = l + 1u;
+                    continue;
+                }
+            }
             starts |= 1ull << l;
             const uint32_t e = l + len;         // the first position after the match
             const uint64_t upto = e >= 64u ? ~0ull : (1ull << e) - 1ull;
@@ -576,7 +656,38 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     }
 }
 
-size_t lds_bytes(uint32_t tile) { return offsetof(Lds, tile) + ((tile + 3u) & ~3u) + 16u; }
+size_t lds_bytes(uint32_t tile, int level) {
+    const uint32_t held = (tile + 3u) & ~3u;
+    return offsetof(Lds, tile) + held + 16u + (level == 2 ? 2u * (held < kLinks ? held : kLinks) : 0u);
+}
+
+template <int kLevel>
+int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride, uint32_t *out_len,
+           uint32_t *crc, void *scratch, void *stream) {
+    if (!tile || tile > kTileMax) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: tile must be 1..65536");
+    if (stride < FC2_DEFLATE_TILE_BOUND(tile))
+        return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: stride below FC2_DEFLATE_TILE_BOUND(tile)");
+    if (!n_bytes) return FC2_OK;
+    if (!src || !dst || !out_len || !crc || !scratch) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: null argument");
+    if (((uintptr_t)scratch & 3u) != 0) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: scratch must be 4-byte aligned");
+    const uint64_t tiles = (n_bytes + tile - 1) / tile;
+    if (tiles > 0x7FFFFFFFull) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: too many tiles for one launch");
+    // the kernel's LDS (over the 64 KiB a kernel gets unasked, for the larger tiles): once per device and level
+    static std::atomic<uint64_t> reserved{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: no current device");
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(reserved.load() & bit)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel<kLevel>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kTileMax, kLevel)) != hipSuccess)
+            return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: cannot reserve the kernel's LDS");
+        reserved |= bit;
+    }
+    hipLaunchKernelGGL(deflate_kernel<kLevel>, dim3((uint32_t)tiles), dim3(64), lds_bytes(tile, kLevel), (hipStream_t)stream,
+                       src, n_bytes, tile, dst, stride, out_len, crc, static_cast<uint32_t *>(scratch));
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_deflate_launch: ") + hipGetErrorString(e));
+}
 
 }  // namespace
 
@@ -588,27 +699,12 @@ extern "C" uint64_t fc2_deflate_scratch_bytes(uint64_t n_bytes, uint32_t tile) {
 
 extern "C" int fc2_deflate_launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride,
                                   uint32_t *out_len, uint32_t *crc, void *scratch, void *stream) {
-    if (!tile || tile > kTileMax) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: tile must be 1..65536");
-    if (stride < FC2_DEFLATE_TILE_BOUND(tile))
-        return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: stride below FC2_DEFLATE_TILE_BOUND(tile)");
-    if (!n_bytes) return FC2_OK;
-    if (!src || !dst || !out_len || !crc || !scratch) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: null argument");
-    if (((uintptr_t)scratch & 3u) != 0) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: scratch must be 4-byte aligned");
-    const uint64_t tiles = (n_bytes + tile - 1) / tile;
-    if (tiles > 0x7FFFFFFFull) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: too many tiles for one launch");
-    // the kernel's LDS (over the 64 KiB a kernel gets unasked, for the larger tiles): once per device
-    static std::atomic<uint64_t> reserved{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: no current device");
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(reserved.load() & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes(kTileMax)) != hipSuccess)
-            return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: cannot reserve the kernel's LDS");
-        reserved |= bit;
-    }
-    hipLaunchKernelGGL(deflate_kernel, dim3((uint32_t)tiles), dim3(64), lds_bytes(tile), (hipStream_t)stream, src, n_bytes,
-                       tile, dst, stride, out_len, crc, static_cast<uint32_t *>(scratch));
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_deflate_launch: ") + hipGetErrorString(e));
+    return launch<1>(src, n_bytes, tile, dst, stride, out_len, crc, scratch, stream);
+}
+
+extern "C" int fc2_deflate_launch_level(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride,
+                                        uint32_t *out_len, uint32_t *crc, void *scratch, void *stream, int level) {
+    if (level == 1) return launch<1>(src, n_bytes, tile, dst, stride, out_len, crc, scratch, stream);
+    if (level == 2) return launch<2>(src, n_bytes, tile, dst, stride, out_len, crc, scratch, stream);
+    return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_level: level is 1 or 2");
 }

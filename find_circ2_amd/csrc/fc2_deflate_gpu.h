@@ -22,8 +22,9 @@ constexpr size_t kMemberOverhead = 18;         // a gzip member's header (10) an
 constexpr double kDefaultTimeout = 60.0;       // seconds a wait for the device may take
 
 // pieces of at most max_piece bytes in tiles of `tile` bytes (1..65536), every wait for the device
-// at most timeout_s seconds (<= 0: kDefaultTimeout); nullptr and err on failure
-Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, std::string &err);
+// at most timeout_s seconds (<= 0: kDefaultTimeout), compressed at `level` (1 or 2:
+// fc2_deflate_launch_level); nullptr and err on failure
+Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, std::string &err);
 // frees everything; a device that timed out is not waited for (its buffers are left to the process's end)
 void gpu_close(Gpu *g);
 size_t gpu_max_piece(const Gpu *g);

@@ -39,6 +39,7 @@ struct Gpu {
     uint32_t tile = kDefaultTile, stride = 0, max_tiles = 0;
     size_t max_piece = 0;
     double timeout_s = kDefaultTimeout;
+    int level = 1;
     bool hung = false;                         // a wait timed out: the device is not touched again
     Slot slot[kSlots];
 };
@@ -49,9 +50,9 @@ static bool hip_ok(hipError_t e, const char *what, std::string &err) {
     return false;
 }
 
-Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, std::string &err) {
-    if (!tile || tile > 65536 || !max_piece || device < 0) {
-        err = "GPU gzip: bad tile, piece size or device";
+Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, std::string &err) {
+    if (!tile || tile > 65536 || !max_piece || device < 0 || level < 1 || level > 2) {
+        err = "GPU gzip: bad tile, piece size, device or level";
         return nullptr;
     }
     Gpu *g = new Gpu();
@@ -60,6 +61,7 @@ Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, std
     g->stride = (FC2_DEFLATE_TILE_BOUND(tile) + 15u) & ~15u;   // slots on 16-byte boundaries: whole vector stores
     g->max_piece = max_piece;
     g->timeout_s = timeout_s > 0 ? timeout_s : kDefaultTimeout;
+    g->level = level;
     g->max_tiles = (uint32_t)((max_piece + tile - 1) / tile);
     const size_t dst = (size_t)g->max_tiles * g->stride, meta = (size_t)g->max_tiles * 2 * sizeof(uint32_t);
     bool ok = hip_ok(hipSetDevice(device), "hipSetDevice", err);
@@ -126,8 +128,8 @@ bool gpu_submit(Gpu *g, int k, const char *data, size_t n, std::string &err) {
     s.busy = true;
     const bool ok =
         hip_ok(hipMemcpyAsync(s.d_src, s.h_src, n, hipMemcpyHostToDevice, s.stream), "upload", err) &&
-        (fc2_deflate_launch(s.d_src, n, g->tile, s.d_dst, g->stride, s.d_meta, s.d_meta + g->max_tiles, s.d_scratch,
-                            s.stream) == FC2_OK || ((err = "GPU gzip: launch failed"), false)) &&
+        (fc2_deflate_launch_level(s.d_src, n, g->tile, s.d_dst, g->stride, s.d_meta, s.d_meta + g->max_tiles, s.d_scratch,
+                                  s.stream, g->level) == FC2_OK || ((err = "GPU gzip: launch failed"), false)) &&
         hip_ok(hipMemcpyAsync(s.h_dst, s.d_dst, (size_t)s.tiles * g->stride, hipMemcpyDeviceToHost, s.stream), "download", err) &&
         hip_ok(hipMemcpyAsync(s.h_meta, s.d_meta, s.tiles * w, hipMemcpyDeviceToHost, s.stream), "download", err) &&
         hip_ok(hipMemcpyAsync(s.h_meta + g->max_tiles, s.d_meta + g->max_tiles, s.tiles * w, hipMemcpyDeviceToHost, s.stream),
@@ -219,8 +221,13 @@ extern "C" uint64_t fc2_gpu_gzip_bound(uint64_t n, uint32_t tile) {
 }
 
 extern "C" int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, void *out, uint64_t cap, uint64_t *out_n) {
+    return fc2_gpu_gzip_level(device, in, n, tile, 1, out, cap, out_n);
+}
+
+extern "C" int fc2_gpu_gzip_level(int device, const void *in, uint64_t n, uint32_t tile, int level, void *out, uint64_t cap,
+                                  uint64_t *out_n) {
     using namespace fc2;
-    if (!tile || tile > 65536 || device < 0 || !out || !out_n || (!in && n))
+    if (!tile || tile > 65536 || device < 0 || !out || !out_n || (!in && n) || level < 1 || level > 2)
         return fc2::fail(FC2_E_PARAM, "fc2_gpu_gzip: bad arguments");
     *out_n = 0;
     char *o = static_cast<char *>(out);
@@ -235,7 +242,7 @@ extern "C" int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t til
     }
     const size_t piece = size_t(4) << 20;
     std::string err;
-    dgz::Gpu *g = dgz::gpu_open(device, piece, tile, 0, err);
+    dgz::Gpu *g = dgz::gpu_open(device, piece, tile, 0, level, err);
     if (!g) return fc2::fail(FC2_E_HIP, "fc2_gpu_gzip: " + err);
     const char *src = static_cast<const char *>(in);
     const uint64_t pieces = (n + piece - 1) / piece;

@@ -48,11 +48,11 @@ class GzPieces {
     }
 
     // device mode: pieces are compressed on GPU `device` from now on, in tiles of `tile` bytes, waiting
-    // at most timeout_s seconds for the device (call right after open()); false and err if the
-    // device's buffers cannot be made (the file then stays on the CPU)
-    bool set_device(int device, uint32_t tile, double timeout_s, std::string &err) {
+    // at most timeout_s seconds for the device, at the compressor's `level` (call right after open()); false
+    // and err if the device's buffers cannot be made (the file then stays on the CPU)
+    bool set_device(int device, uint32_t tile, double timeout_s, int level, std::string &err) {
         if (!f_ || gpu_ || wrote_any_) { err = "GPU gzip: set the device once, after open and before any text"; return false; }
-        gpu_ = dgz::gpu_open(device, 2 * piece_, tile ? tile : dgz::kDefaultTile, timeout_s, err);   // (append_owned: up to two pieces long)
+        gpu_ = dgz::gpu_open(device, 2 * piece_, tile ? tile : dgz::kDefaultTile, timeout_s, level, err);   // (append_owned: up to two pieces long)
         device_mode_ = gpu_ != nullptr;
         return device_mode_;
     }

@@ -641,6 +641,7 @@ struct fc2_ingest {
     bool bam_stopped = false;    // the reference raised inside process_mate: nothing after it is written
     std::string bam_err;
     uint64_t bam_gpu_pieces = 0, bam_cpu_pieces = 0;    // fc2_ingest_bam_out_counts, once the writer is closed
+    int bam_level = 1;                          // fc2_ingest_set_bam_out_device_level
     // grouping state
     bool started = false;
     Mate current, other;
@@ -2401,8 +2402,18 @@ extern "C" int fc2_ingest_set_bam_out_device(fc2_ingest *h, int mode, int device
         return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: mode is 0, 1 or 2, block at most 0xff00, "
                                       "piece_blocks at most 1024");
     std::string err;
-    if (!fc2::bam::set_device(h->bam_out, mode, device, block, piece_blocks, timeout_s, err))
+    if (!fc2::bam::set_device(h->bam_out, mode, device, block, piece_blocks, timeout_s, h->bam_level, err))
         return fc2::fail(mode == 1 ? FC2_E_HIP : FC2_E_PARAM, "fc2_ingest_set_bam_out_device: " + err);
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_set_bam_out_device_level(fc2_ingest *h, int level) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_level: null argument");
+    if (!h->bam_out || h->n_records || fc2::bam::device_set(h->bam_out))
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_level: call after fc2_ingest_set_bam_out, before "
+                                      "fc2_ingest_set_bam_out_device and before reading");
+    if (level < 1 || level > 2) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_level: level is 1 or 2");
+    h->bam_level = level;
     return FC2_OK;
 }
 

@@ -127,6 +127,10 @@ int fc2_caller_set_reads_gz_device(fc2_caller *h, int device);
  * set afterwards with fc2_caller_set_reads_gz_device.  The command line passes FC2_GPU_GZIP_TILE and
  * FC2_GPU_GZIP_TIMEOUT_S here; the library itself reads no environment variable for them. */
 int fc2_caller_set_reads_gz_device_tuning(fc2_caller *h, uint32_t tile, double timeout_s);
+/* This handle's compression level on the device (1, the default, or 2: fc2_deflate_launch_level), for the device
+ * mode set afterwards with fc2_caller_set_reads_gz_device; FC2_E_PARAM for another level or a call after it.
+ * The command line passes FC2_GPU_GZIP_LEVEL here. */
+int fc2_caller_set_reads_gz_device_level(fc2_caller *h, int level);
 /* pieces the device compressed, and pieces of the device mode the CPU compressed, so far (0, 0 without it) */
 int fc2_caller_reads_gz_counts(const fc2_caller *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces);
 
@@ -141,10 +145,18 @@ int fc2_caller_reads_gz_counts(const fc2_caller *h, uint64_t *gpu_pieces, uint64
  * (not expected; the caller compresses it). */
 int fc2_deflate_launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride,
                        uint32_t *out_len, uint32_t *crc, void *scratch, void *stream);
+/* fc2_deflate_launch at `level`: 1 is fc2_deflate_launch itself; 2 searches deeper (chains of up to 8
+ * candidates per position and a lazy step, csrc/fc2_deflate.hip) for smaller streams of the same form, with the
+ * same arguments, scratch and bound.  Any other level: FC2_E_PARAM, before the device is touched. */
+int fc2_deflate_launch_level(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride,
+                             uint32_t *out_len, uint32_t *crc, void *scratch, void *stream, int level);
 uint64_t fc2_deflate_scratch_bytes(uint64_t n_bytes, uint32_t tile);
 /* one buffer through the host path of spliced_reads.fastq.gz's device mode, for tests and other hosts: gzip
  * members (one per tile) of in[0, n) into out (cap bytes); FC2_E_RANGE if they do not fit. */
 int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, void *out, uint64_t cap, uint64_t *out_n);
+/* fc2_gpu_gzip with the tiles compressed at `level` (1 or 2, fc2_deflate_launch_level; else FC2_E_PARAM) */
+int fc2_gpu_gzip_level(int device, const void *in, uint64_t n, uint32_t tile, int level, void *out, uint64_t cap,
+                       uint64_t *out_n);
 uint64_t fc2_gpu_gzip_bound(uint64_t n, uint32_t tile);
 
 /* ---- BGZF output on the GPU (csrc/fc2_bgzf_out.hip; the rule: csrc/fc2_bgzf_frame_impl.h) ---- */
@@ -169,6 +181,9 @@ int fc2_bgzf_frame_host(const uint8_t *slots, uint32_t stride, const uint32_t *o
  * blocks do not fit, FC2_E_PARAM for a block outside 1..0xff00. */
 int fc2_gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, void *out,
                  uint64_t cap, uint64_t *out_n);
+/* fc2_gpu_bgzf with the blocks compressed at `level` (1 or 2, fc2_deflate_launch_level; else FC2_E_PARAM) */
+int fc2_gpu_bgzf_level(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, int level,
+                       void *out, uint64_t cap, uint64_t *out_n);
 uint64_t fc2_gpu_bgzf_bound(uint64_t n, uint32_t block);
 
 /* The BED rows (no header) of 0 = circ_splice_sites.bed, 1 = lin_splice_sites.bed

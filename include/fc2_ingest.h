@@ -96,6 +96,10 @@ int fc2_ingest_close_bam_out(fc2_ingest *h);
  * At the defaults the four slots hold 31.9 MiB of pinned host and 111.6 MiB of device memory. */
 int fc2_ingest_set_bam_out_device(fc2_ingest *h, int mode, int device, uint32_t block, uint32_t piece_blocks,
                                   double timeout_s);
+/* The level mode 1 compresses at (1, the default, or 2: fc2_deflate_launch_level, include/fc2_caller.h), for the
+ * device mode set afterwards with fc2_ingest_set_bam_out_device; mode 2 ignores it.  FC2_E_PARAM for another
+ * level or a call after reading has begun.  The command line passes FC2_GPU_BAM_LEVEL here. */
+int fc2_ingest_set_bam_out_device_level(fc2_ingest *h, int level);
 /* pieces the device (mode 2: its host model) compressed, and pieces of the device mode zlib compressed, so
  * far; final after fc2_ingest_close_bam_out (0, 0 without the device mode) */
 int fc2_ingest_bam_out_counts(const fc2_ingest *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces);

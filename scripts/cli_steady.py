@@ -23,6 +23,11 @@ usage: python scripts/cli_steady.py [--sizes 2000000,20000000] [--threads 4,8,16
 --sites K: the spliced reads cross K planted junctions (many reads per junction, as in a real
 library) instead of one junction each (the junction tables then stay small).
 -B: every run writes spliced_alignments.bam too (the CLI's -B; --variants FC2_GPU_BAM=1 compresses it on the GPU).
+--variants: each comma-separated entry is a run of its own; an entry may hold several settings joined by "+"
+(FC2_GPU_BAM=1+FC2_GPU_BAM_LEVEL=2).  Mind the comma: "FC2_GPU_BAM=1,FC2_GPU_BAM_LEVEL=2" is two runs, the
+second with the level alone, which the command line does not read without FC2_GPU_BAM=1; the comma kept its
+meaning so that earlier command lines measure what they measured.  Every record carries the sizes of the two
+compressed output files.
 Each run's record is printed as its own JSON line as soon as it is done; the summary comes last.
 """
 import argparse
@@ -135,7 +140,10 @@ def run_cli(fa, bam, out, threads, extra=(), timeout=900, timing=False, by_path=
     sd = re.search(r"process shutdown: (.*)", text)
     if sd:
         phases.update({"shutdown_" + k: float(v) for k, v in re.findall(r"(\w+)=([0-9.naN]+)", sd.group(1))})
+    sizes = {f: os.path.getsize(os.path.join(out, f)) for f in ("spliced_reads.fastq.gz", "spliced_alignments.bam")
+             if os.path.exists(os.path.join(out, f))}
     return {
+        "output_bytes": sizes, "levels": {k: int(v) for k, v in phases.items() if k.endswith("_gpu_level")},
         "threads": threads, "cpus": len(cpus) if cpus else None, "process_wall_s": round(wall, 3),
         "reads": reads, "spans": spans,
         "loop_s": loop_s, "genome_wait_s": phases.get("genome_wait_s"),
@@ -210,7 +218,7 @@ def main():
     ap.add_argument("--keep", action="store_true")
     ap.add_argument("--variants", default="",
                     help="comma-separated K=V environment settings, each run as well as the default "
-                         "(e.g. FC2_GPU_INFLATE=0)")
+                         "(e.g. FC2_GPU_INFLATE=0); K=V+K2=V2 sets both in one run")
     ap.add_argument("--sites", type=int, default=0,
                     help="junction sites the spliced reads cross (scripts/gen_reads.c); 0: one per read")
     ap.add_argument("-B", "--bam", action="store_true", help="run the CLI with -B (spliced_alignments.bam)")
@@ -236,9 +244,9 @@ def main():
                 # the clean runs (what a user gets), then one with FC2_CALLER_TIMING's per-stage CPU
                 # accounting (it also closes the caller at exit to print the totals)
                 for r in list(range(a.reps)) + ["timing"]:
-                    out = os.path.join(d, "o_%d_%d_%s%s" % (n, t, r, "_" + var.replace("=", "") if var else ""))
+                    out = os.path.join(d, "o_%d_%d_%s%s" % (n, t, r, "_" + var.replace("=", "").replace("+", "_") if var else ""))
                     x = run_cli(fa, bams[n], out, t, extra=extra, timing=(r == "timing"),
-                                env_extra=dict([var.split("=", 1)]) if var else None)
+                                env_extra=dict(kv.split("=", 1) for kv in var.split("+")) if var else None)
                     x["size"] = n
                     x["rep"] = r
                     x["variant"] = var or "default"

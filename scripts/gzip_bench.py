@@ -4,9 +4,11 @@ fc2_deflate_launch in one launch and in launches of --piece bytes (the writer's 
 HIP events on the launch stream; with both copies (fc2_gpu_gzip: pinned staging, upload, kernel,
 download, members assembled) on the wall clock; every tile's stream checked with zlib.  The CPU legs
 are libdeflate level 1 (the default writer; fc2_deflate.h) and zlib level 1 on one core over the same
-bytes.  One JSON line.  Measurement infrastructure (not part of the product).
+bytes, and zlib level 6 over each tile alone (what a BGZF writer at its default makes of the same cuts).
+--level 2 runs the compressor's second level (fc2_deflate_launch_level).  One JSON line.  Measurement
+infrastructure (not part of the product).
 
-usage: python scripts/gzip_bench.py [--reads N | --text FILE] [--tile T] [--piece P] [--reps R]
+usage: python scripts/gzip_bench.py [--reads N | --text FILE] [--tile T] [--piece P] [--reps R] [--level 1|2]
 """
 import argparse
 import ctypes
@@ -66,6 +68,7 @@ def main():
     ap.add_argument("--tile", type=int, default=32768)
     ap.add_argument("--piece", type=int, default=4 << 20)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--level", type=int, default=1, choices=[1, 2])
     a = ap.parse_args()
     import torch
     from find_circ2_amd import _native as N
@@ -85,12 +88,14 @@ def main():
 
     def launch(t0, t1):
         b0, b1 = t0 * tile, min(n, t1 * tile)
-        N.check(L.fc2_deflate_launch(src.data_ptr() + b0, b1 - b0, tile, dst.data_ptr() + t0 * stride, stride,
-                                     ln.data_ptr() + 4 * t0, cr.data_ptr() + 4 * t0, scratch.data_ptr() + 4 * b0,
-                                     ctypes.c_void_p(stream.cuda_stream)))
+        N.check(L.fc2_deflate_launch_level(src.data_ptr() + b0, b1 - b0, tile, dst.data_ptr() + t0 * stride, stride,
+                                           ln.data_ptr() + 4 * t0, cr.data_ptr() + 4 * t0, scratch.data_ptr() + 4 * b0,
+                                           ctypes.c_void_p(stream.cuda_stream), a.level))
+
+    spread = {}                                     # every repetition's ms, by tiles per launch
 
     def timed(step):
-        best = None
+        best, every = None, []
         for _ in range(a.reps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
@@ -99,7 +104,9 @@ def main():
             e1.record(stream)
             torch.cuda.synchronize()
             ms = e0.elapsed_time(e1)
+            every.append(round(ms, 3))
             best = ms if best is None else min(best, ms)
+        spread[step] = every
         return best
 
     launch(0, tiles)
@@ -124,7 +131,7 @@ def main():
     wall = None
     for _ in range(max(2, a.reps)):
         t0 = time.time()
-        N.check(L.fc2_gpu_gzip(0, text, n, tile, buf, cap, ctypes.byref(got)))
+        N.check(L.fc2_gpu_gzip_level(0, text, n, tile, a.level, buf, cap, ctypes.byref(got)))
         s = time.time() - t0
         wall = s if wall is None else min(wall, s)
     host_ok = gzip.decompress(bytes(bytearray(buf)[:got.value])) == text
@@ -132,10 +139,16 @@ def main():
     t0 = time.time()
     zl = sum(len(zlib.compress(text[b0:b0 + (4 << 20)], 1)) for b0 in range(0, n, 4 << 20))
     zl_s = time.time() - t0
+    z6 = 0
+    for b0 in range(0, n, tile):                    # raw streams, as the GPU's are counted
+        c = zlib.compressobj(6, zlib.DEFLATED, -15)
+        z6 += len(c.compress(text[b0:b0 + tile])) + len(c.flush())
     print(json.dumps({
-        "text_bytes": n, "tile": tile, "tiles": tiles, "bad_tiles": int(bad), "host_path_ok": bool(host_ok),
+        "text_bytes": n, "level": a.level, "tile": tile, "tiles": tiles, "bad_tiles": int(bad), "host_path_ok": bool(host_ok),
         "gpu_stream_bytes": int(lens.sum()), "gpu_gzip_bytes": int(got.value),
         "gpu_ratio": round(int(got.value) / n, 4),
+        "zlib6_per_tile_stream_bytes": z6, "gpu_over_zlib6_per_tile": round(int(lens.sum()) / z6, 4),
+        "gpu_one_launch_ms_every": spread[tiles], "gpu_pieces_ms_every": spread[per],
         "gpu_one_launch_ms": round(ms_all, 3), "gpu_one_launch_GBps": round(n / ms_all / 1e6, 2),
         "gpu_piece_bytes": per * tile, "gpu_pieces_ms": round(ms_piece, 3), "gpu_pieces_GBps": round(n / ms_piece / 1e6, 2),
         "gpu_with_copies_s": round(wall, 4), "gpu_with_copies_GBps": round(n / wall / 1e9, 3),
