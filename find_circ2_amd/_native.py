@@ -166,6 +166,7 @@ EXPORTED = [
     "fc2_caller_set_reads_gz", "fc2_caller_close_reads", "fc2_caller_set_reads_gz_device", "fc2_caller_reads_gz_counts",
     "fc2_deflate_launch", "fc2_deflate_scratch_bytes", "fc2_gpu_gzip", "fc2_gpu_gzip_bound", "fc2_caller_set_reads_gz_device_tuning",
     "fc2_deflate_launch_level", "fc2_gpu_gzip_level", "fc2_gpu_bgzf_level", "fc2_caller_set_reads_gz_device_level",
+    "fc2_deflate_launch_hist", "fc2_gpu_gzip_hist", "fc2_caller_set_reads_gz_device_history",
     "fc2_bgzf_frame_launch", "fc2_bgzf_frame_host", "fc2_gpu_bgzf", "fc2_gpu_bgzf_bound",
     # include/fc2_ctx.h
     "fc2_ctx_create", "fc2_ctx_create_sibling", "fc2_ctx_destroy", "fc2_ctx_genome_load", "fc2_ctx_genome_view", "fc2_ctx_scan_async",
@@ -329,6 +330,9 @@ def lib() -> ctypes.CDLL:
         "fc2_caller_set_reads_gz_device_level": (ctypes.c_int, [vp, ctypes.c_int]),
         "fc2_deflate_launch_level": (ctypes.c_int, [vp, u64, u32, vp, u32, vp, vp, vp, vp, ctypes.c_int]),
         "fc2_gpu_gzip_level": (ctypes.c_int, [ctypes.c_int, vp, u64, u32, ctypes.c_int, vp, u64, P(u64)]),
+        "fc2_caller_set_reads_gz_device_history": (ctypes.c_int, [vp, u32]),
+        "fc2_deflate_launch_hist": (ctypes.c_int, [vp, u64, u32, u32, vp, u32, vp, vp, vp, vp, ctypes.c_int]),
+        "fc2_gpu_gzip_hist": (ctypes.c_int, [ctypes.c_int, vp, u64, u32, u32, ctypes.c_int, vp, u64, P(u64)]),
         "fc2_caller_rows": (ctypes.c_int, [vp, ctypes.c_int, P(ctypes.c_void_p), P(u64)]),
         "fc2_caller_write_rows": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, P(u64)]),
         "fc2_caller_counter": (ctypes.c_int, [vp, ctypes.c_int, P(ctypes.c_char_p), P(ctypes.c_double)]),

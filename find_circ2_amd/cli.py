@@ -307,13 +307,16 @@ def _gzip_device(options):
     """spliced_reads.fastq.gz compressed on the GPU: only with FC2_GPU_GZIP=1, on the first of
     the run's devices, in tiles of FC2_GPU_GZIP_TILE bytes (32768), waiting at most
     FC2_GPU_GZIP_TIMEOUT_S seconds (60) for the device, at the compressor's level 2 with FC2_GPU_GZIP_LEVEL=2
-    (unset or anything else: level 1).  Anything but 1: {}, the worker threads compress."""
+    (unset or anything else: level 1), every tile referring to the FC2_GPU_GZIP_HISTORY bytes of its piece
+    before it (unset, empty or 0: none; DESIGN.md §5 "History across the tiles").  Anything but 1: {}, the
+    worker threads compress."""
     if os.environ.get("FC2_GPU_GZIP") != "1":
         return {}
     from .ctxpipe import device_index
     return dict(gzip_device=device_index(options.device), gzip_tile=int(os.environ.get("FC2_GPU_GZIP_TILE") or 0),
                 gzip_timeout_s=float(os.environ.get("FC2_GPU_GZIP_TIMEOUT_S") or 0),
-                gzip_level=2 if os.environ.get("FC2_GPU_GZIP_LEVEL") == "2" else 1)
+                gzip_level=2 if os.environ.get("FC2_GPU_GZIP_LEVEL") == "2" else 1,
+                gzip_history=int(os.environ.get("FC2_GPU_GZIP_HISTORY") or 0))
 
 
 def _bam_device(options):
@@ -412,6 +415,7 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
             if nc.bam_device:
                 startup.update(zip(("bam_gpu_pieces", "bam_cpu_pieces"), nc.bam_out_pieces))
             levels = (", gzip_gpu_level=2" if nc.gzip_device is not None and nc.gzip_level == 2 else "") + \
+                (", gzip_gpu_history=%d" % nc.gzip_history if nc.gzip_device is not None and nc.gzip_history > 0 else "") + \
                 (", bam_gpu_level=2" if nc.bam_device and nc.bam_device.get("level") == 2 else "")
             logger.info("process phases: " + ", ".join("%s=%.3f" % kv for kv in startup.items()) + levels +
                         ", process_age_s=%.3f, numpy_loaded=%d, torch_loaded=%d"

@@ -889,6 +889,7 @@ struct fc2_caller {
     uint32_t gz_tile = 0;                       // fc2_caller_set_reads_gz_device_tuning (0: the defaults)
     double gz_timeout_s = 0;
     int gz_level = 1;                           // fc2_caller_set_reads_gz_device_level
+    uint32_t gz_hist = 0;                       // fc2_caller_set_reads_gz_device_history
     uint64_t n_chunks = 0;                      // chunks formed (next side)
 };
 
@@ -2704,7 +2705,9 @@ extern "C" int fc2_caller_set_reads_gz_device(fc2_caller *h, int device) {
         return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: call once, after fc2_caller_set_reads_gz and before "
                                       "the first fc2_caller_submit");
     std::string err;
-    if (!h->reads_gz.set_device(device, h->gz_tile, h->gz_timeout_s, h->gz_level, err)) return fc2::fail(FC2_E_HIP, "fc2_caller_set_reads_gz_device: " + err);
+    if ((h->gz_tile ? h->gz_tile : fc2::dgz::kDefaultTile) + h->gz_hist > 65536)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: tile + history over 65536 (the CPU writer stays)");
+    if (!h->reads_gz.set_device(device, h->gz_tile, h->gz_timeout_s, h->gz_level, h->gz_hist, err)) return fc2::fail(FC2_E_HIP, "fc2_caller_set_reads_gz_device: " + err);
     return FC2_OK;
 }
 
@@ -2724,6 +2727,15 @@ extern "C" int fc2_caller_set_reads_gz_device_level(fc2_caller *h, int level) {
     if (h->reads_gz.device_mode())
         return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_level: call before fc2_caller_set_reads_gz_device");
     h->gz_level = level;
+    return FC2_OK;
+}
+
+extern "C" int fc2_caller_set_reads_gz_device_history(fc2_caller *h, uint32_t hist) {
+    if (!h || hist > 32768)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_history: null handle, or a history over 32768 bytes");
+    if (h->reads_gz.device_mode())
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_history: call before fc2_caller_set_reads_gz_device");
+    h->gz_hist = hist;
     return FC2_OK;
 }
 

@@ -1,7 +1,8 @@
 // fc2_deflate.hip -- DEFLATE compression on the GPU: the gzip members of spliced_reads.fastq.gz
 // (fc2_gzpieces.h's device mode, fc2_deflate_gpu.hip), the mirror image of fc2_inflate.hip.
 //
-// The text is cut into tiles of at most 64 KiB; a tile never refers to bytes before its own start,
+// The text is cut into tiles of at most 64 KiB; a tile never refers to bytes before its own start
+// (but with a history, below: then to input bytes of its launch, never to another tile's output),
 // so tiles are independent: one wavefront per tile, no waits between workgroups.  Each tile becomes
 // one complete raw DEFLATE stream (RFC 1951) -- a single dynamic-Huffman block, or stored block(s)
 // when that would not be smaller -- with the gzip CRC-32 of its input beside it, so the host only
@@ -53,6 +54,48 @@
 // n + 16, as at level 1.  Level 2 adds no store to global memory.
 //   LDS at level 2: 2 bytes more per position of the window: 120860 B with a tile of 32 KiB, 153372 B
 // at 0xff00, 153628 B at 64 KiB -- one workgroup a CU at every tile over some 19 KiB.
+//
+// History (deflate_kernel<level, true>, fc2_deflate_launch_hist; tests/deflate_model_hist.py is the rule in
+// Python, bit-exact).  The launch's n bytes are one DEFLATE stream cut into tiles.  Tile i covers
+// src[i * tile, min(n, (i + 1) * tile)); its history is the h = min(hist, i * tile) input bytes before it --
+// input, so no tile waits for another's output -- and the launch's first tile has none.  LDS holds the region:
+// history and tile back to back, m = h + (the tile's bytes) <= 65536 bytes; positions are counted from the
+// history's first byte, the tile starts at position h.
+//   Steps.  Pass 1 steps over the whole region 64 positions at a time from position 0 (base = 0, 64, ...), so
+// one step may hold the history's last positions and the tile's first.  Every position with p + 4 <= m, of
+// the history or of the tile (a history position's four bytes may run into the tile), enters the heads and at
+// level 2 writes its link[] entry exactly as above: read first, then atomicMax.  Pass 1 starts with skip = h
+// in place of 0: the history lies "inside a match" that ends where the tile begins, and that alone keeps a
+// history position from searching and from giving a token (a step wholly inside it is left after it has
+// entered its positions; a step across the boundary has its history lanes covered).
+//   Matches.  A tile position searches as above; its candidate is any earlier position, of the history too.
+// The distance limit stays 32768, the length limit min(258, m - p): the end of the tile.  A match whose
+// source starts in the history and runs into the tile is an ordinary overlapping match.
+//   Not the history's: the bytes' histogram and with it the literal cost (taken over positions h .. m, divided
+// by the tile's length), the CRC-32 (crc[i] is the CRC of the tile's own bytes, read at any byte offset of the
+// region), the tokens, and so ISIZE.
+//   Stream.  The launch's last tile is written as above, BFINAL = 1.  Every other tile writes its dynamic block
+// with BFINAL = 0 and an empty stored block behind it -- bits 000, zeros to the byte boundary, 00 00 FF FF, at
+// most 5 bytes -- so its stream ends on a byte boundary and the streams back to back are one stream.  The
+// Huffman form is used only where its estimate with those bytes counted, ((header + data bits + 3 + 7) >> 3)
+// + 4, is below the stored form's n + 5 (n + 10 at 65536); the stored form is written as non-final stored
+// blocks with nothing after them.  Both stay within tile + 16.
+//   link[] with a history.  The bounds argument above holds word for word with n read as m, the region's
+// length: link[] has min(tile + hist rounded up to 4, 32768) entries behind the region's padding; a store is at
+// p & 32767 with p < m <= tile + hist <= 65536; a load at c & 32767 with c < p; a history position enters
+// itself and writes its entry like any other, so every c walked has written its entry; with m > 32768 the slot
+// of c is reused by c + 32768, and the walk ends where c + 32768 < base + 64 as before.  Region bytes are read
+// up to c + 258 + 3 < m + 16.  Nothing changes in the scratch (a token per tile byte at most: history
+// positions give none) or in FC2_DEFLATE_TILE_BOUND.
+//   Instantiations.  The history is a template parameter: <1, false> and <2, false> are the kernels above --
+// the same instructions as before the history existed, one more (unread) kernel argument -- and `hist = 0`
+// goes to them.  (A body shared by two kernels with the former arguments was tried: inlined there, the compiler
+// orders and allocates it otherwise.)  Compiler's resource report for gfx950 (VGPRs, SGPRs, scratch; dynamic LDS
+// only):
+//   <1, false> 48, 72, 0    <2, false> 48, 72, 0    <1, true> 47, 74, 0    <2, true> 47, 78, 0
+//   LDS with a history: 22540 B + (tile + hist rounded up to 4) + 16, and at level 2 two bytes more per
+// position up to 32768.  Level 1: 8 KiB + 32 KiB 63516 B (two workgroups a CU), 32 KiB + 32 KiB 88092 B
+// (one).  Level 2: 8 KiB + 32 KiB 129052 B, 32 KiB + 32 KiB 153628 B (one a CU both).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -289,22 +332,32 @@ __device__ __forceinline__ void put(Lds &L, Out &o, uint32_t v, uint32_t nb) {
     o.bit += nb;
 }
 
-template <int kLevel>
+// kHist: the launch is one DEFLATE stream, and a tile has the `hist` bytes before it in front of it in LDS
+// (the header's "History"); without it `hist` is not looked at.
+template <int kLevel, bool kHist>
 __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__ src, uint64_t n_bytes, uint32_t tile,
                                                      uint8_t *__restrict__ dst, uint32_t stride,
                                                      uint32_t *__restrict__ out_len, uint32_t *__restrict__ crc,
-                                                     uint32_t *__restrict__ scratch) {
+                                                     uint32_t *__restrict__ scratch, uint32_t hist) {
     extern __shared__ __align__(16) uint8_t smem[];
     Lds &L = *reinterpret_cast<Lds *>(smem);
     uint32_t *T = L.tile;
     uint16_t *link = nullptr;                  // level 2's links, behind the tile and its 16 bytes of padding (lds_bytes)
-    if constexpr (kLevel == 2) link = reinterpret_cast<uint16_t *>(smem + offsetof(Lds, tile) + ((tile + 3u) & ~3u) + 16u);
+    if constexpr (kLevel == 2) {
+        if constexpr (kHist) link = reinterpret_cast<uint16_t *>(smem + offsetof(Lds, tile) + ((tile + hist + 3u) & ~3u) + 16u);
+        else link = reinterpret_cast<uint16_t *>(smem + offsetof(Lds, tile) + ((tile + 3u) & ~3u) + 16u);
+    }
     const uint32_t blk = blockIdx.x;
     const int lane = (int)threadIdx.x;
     const uint64_t start = (uint64_t)blk * tile;
     if (start >= n_bytes) return;
     const uint32_t n = (uint32_t)(n_bytes - start < (uint64_t)tile ? n_bytes - start : (uint64_t)tile);   // 1..65536
-    const uint8_t *in = src + start;
+    // the region in LDS: h bytes of history, then the tile; m bytes, positions counted from the history's first
+    uint32_t h = 0;
+    if constexpr (kHist) h = (uint32_t)(start < (uint64_t)hist ? start : (uint64_t)hist);
+    const uint32_t m = h + n;                   // 1..65536
+    const bool last = !kHist || start + n >= n_bytes;   // written as a stream of its own: BFINAL, nothing after it
+    const uint8_t *in = src + start - h;
     uint8_t *slot = dst + (uint64_t)blk * stride;
     uint32_t *tok = scratch + start;           // n tokens at most
 
@@ -314,11 +367,11 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     for (uint32_t k = (uint32_t)lane; k < 288u; k += 64) L.lfreq[k] = 0;
     if (lane < 32) L.dfreq[lane] = 0;
     if (lane < 20) L.cfreq[lane] = 0;
-    const uint32_t nw = (n + 3u) >> 2;         // words holding the tile; four more are zeroed
+    const uint32_t nw = (m + 3u) >> 2;         // words holding the region; four more are zeroed
     __syncthreads();
     if (((uintptr_t)in & 15u) == 0) {
-        for (uint32_t b0 = 16u * (uint32_t)lane; b0 < n; b0 += 1024u) {
-            if (b0 + 16u <= n) {
+        for (uint32_t b0 = 16u * (uint32_t)lane; b0 < m; b0 += 1024u) {
+            if (b0 + 16u <= m) {
                 const uint4 v = *reinterpret_cast<const uint4 *>(in + b0);
                 T[b0 >> 2] = v.x; T[(b0 >> 2) + 1] = v.y; T[(b0 >> 2) + 2] = v.z; T[(b0 >> 2) + 3] = v.w;
             } else {
@@ -326,7 +379,7 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
                     uint32_t v = 0;
                     for (uint32_t i = 0; i < 4u; ++i) {
                         const uint32_t p = b0 + 4u * w + i;
-                        if (p < n) v |= (uint32_t)in[p] << (8u * i);
+                        if (p < m) v |= (uint32_t)in[p] << (8u * i);
                     }
                     T[(b0 >> 2) + w] = v;      // (words up to nw + 3 at most: inside the 16 bytes of padding)
                 }
@@ -337,7 +390,7 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
             uint32_t v = 0;
             for (uint32_t i = 0; i < 4u; ++i) {
                 const uint32_t p = 4u * k + i;
-                if (p < n) v |= (uint32_t)in[p] << (8u * i);
+                if (p < m) v |= (uint32_t)in[p] << (8u * i);
             }
             T[k] = v;
         }
@@ -348,17 +401,23 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     for (uint32_t k = (uint32_t)lane; k < nw; k += 64) {
         const uint32_t v = T[k];
         for (uint32_t i = 0; i < 4u; ++i)
-            if (4u * k + i < n) atomicAdd(&L.lfreq[(v >> (8u * i)) & 255u], 1u);
+            if (4u * k + i >= h && 4u * k + i < m) atomicAdd(&L.lfreq[(v >> (8u * i)) & 255u], 1u);
     }
     uint32_t R = 0;                             // raw CRC, in rows of 1024 bytes as the inflater's
     uint32_t done = 0;
     for (; done + 1024u <= n; done += 1024u) {
-        const uint32_t k = (done >> 2) + 4u * (uint32_t)lane;
-        const uint32_t c = crc_word(crc_word(crc_word(crc_word(0u, T[k]), T[k + 1]), T[k + 2]), T[k + 3]);
+        uint32_t c;
+        if constexpr (kHist) {                  // (the tile's own bytes: at any byte offset of the region)
+            const uint32_t q = h + done + 16u * (uint32_t)lane;
+            c = crc_word(crc_word(crc_word(crc_word(0u, load32u(T, q)), load32u(T, q + 4u)), load32u(T, q + 8u)), load32u(T, q + 12u));
+        } else {
+            const uint32_t k = (done >> 2) + 4u * (uint32_t)lane;
+            c = crc_word(crc_word(crc_word(crc_word(0u, T[k]), T[k + 1]), T[k + 2]), T[k + 3]);
+        }
         R = multmodp(kX2n[13], R) ^ wave_fold(c);
     }
     for (; done < n; ++done) {                  // the last, short row byte by byte, on every lane alike
-        R ^= (T[done >> 2] >> (8u * (done & 3u))) & 255u;
+        R ^= (T[(h + done) >> 2] >> (8u * ((h + done) & 3u))) & 255u;
 #pragma unroll
         for (int b = 0; b < 8; ++b) R = mulx(R);
     }
@@ -382,12 +441,12 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     __syncthreads();
 
     // ---- pass 1: matches, tokens, histograms ------------------------------------------------------
-    uint32_t ntok = 0, skip = 0;                // tokens so far; positions below `skip` are inside a match
+    uint32_t ntok = 0, skip = h;                // tokens so far; positions below `skip` are inside a match, or history
     uint32_t extra = 0;                         // this lane's tokens' extra bits
-    for (uint32_t base = 0; base < n; base += 64) {
+    for (uint32_t base = 0; base < m; base += 64) {
         const uint32_t p = base + (uint32_t)lane;
-        const bool can = p + kMinMatch <= n;
-        const uint32_t v = load32u(T, p < n ? p : 0u);
+        const bool can = p + kMinMatch <= m;
+        const uint32_t v = load32u(T, p < m ? p : 0u);
         const uint32_t h = (v * 2654435761u) >> (32 - kHashBits);
         const uint32_t cand = can ? L.htab[h] : 0u;
         __syncthreads();
@@ -400,7 +459,7 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
         uint32_t mlen = 0, mdist = 0;
         if constexpr (kLevel == 2) {
             if (cand && p >= skip) {
-                const uint32_t maxlen = n - p < kMaxMatch ? n - p : kMaxMatch;
+                const uint32_t maxlen = m - p < kMaxMatch ? m - p : kMaxMatch;
                 uint32_t c = cand - 1u, best = 0, bestd = 0;
                 for (int k = 0; k < kDepth; ++k) {
                     const uint32_t d = p - c;
@@ -438,7 +497,7 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
             const uint32_t c = cand - 1u;       // < p: positions of earlier steps only
             const uint32_t d = p - c;
             if (d <= kMaxDist && load32u(T, c) == v) {
-                const uint32_t maxlen = n - p < kMaxMatch ? n - p : kMaxMatch;
+                const uint32_t maxlen = m - p < kMaxMatch ? m - p : kMaxMatch;
                 uint32_t l = 4;
                 while (l < maxlen) {
                     const uint32_t x = load32u(T, c + l) ^ load32u(T, p + l);
@@ -481,7 +540,7 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
             cur = e;
             skip = base + e;
         }
-        const bool emit = p < n && !((cov >> lane) & 1ull);
+        const bool emit = p < m && !((cov >> lane) & 1ull);
         const uint64_t em = __ballot(emit);
         if (emit) {
             const uint32_t at = ntok + (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
@@ -573,7 +632,7 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     o.over = false;
     const uint32_t stored_bytes = n + (n > 65535u ? 10u : 5u);
     if (lane == 0 && ok) {                      // the block's header
-        put(L, o, 1u | (2u << 1), 3);           // BFINAL, dynamic codes
+        put(L, o, (last ? 1u : 0u) | (2u << 1), 3);   // BFINAL, dynamic codes
         uint32_t hclen = 19;
         while (hclen > 4u && L.clen[kDClOrder[hclen - 1u]] == 0) --hclen;
         put(L, o, hlit - 257u, 5);
@@ -588,7 +647,9 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     }
     o.bit = ((uint64_t)uni((uint32_t)(o.bit >> 32)) << 32) | uni((uint32_t)o.bit);
     __syncthreads();
-    const uint32_t dyn_bytes = (uint32_t)((o.bit - 8ull * o.a + data_bits + 7u) >> 3);
+    // (a tile that is not the last: the empty stored block behind it counted, 3 bits, the padding and 4 bytes)
+    const uint32_t dyn_bytes = last ? (uint32_t)((o.bit - 8ull * o.a + data_bits + 7u) >> 3)
+                                    : (uint32_t)((o.bit - 8ull * o.a + data_bits + 3u + 7u) >> 3) + 4u;
     uint32_t len;
     if (ok && dyn_bytes < stored_bytes) {
         for (uint32_t b0 = 0; b0 < ntok; b0 += 64) {
@@ -625,6 +686,13 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
         }
         if (lane == 0) or_bits(L, o, o.bit, L.lcode[256], L.llen[256]);
         o.bit += L.llen[256];
+        if constexpr (kHist) {
+            if (!last) {                        // bits 000, zeros to the byte boundary, 00 00 FF FF
+                o.bit = (o.bit + 3u + 7u) & ~7ull;
+                if (lane == 0) or_bits(L, o, o.bit, 0xFFFF0000ull, 32);
+                o.bit += 32u;
+            }
+        }
         __syncthreads();
         const uint32_t end = (uint32_t)((o.bit + 7u) >> 3);
         store_pieces(L, o, end, lane);
@@ -636,15 +704,15 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
             const uint32_t first = n > 65535u ? 65535u : n;
             uint32_t b;
             if (k < 5u) {
-                const uint32_t hd[5] = {n > 65535u ? 0u : 1u, first & 255u, first >> 8, ~first & 255u, (~first >> 8) & 255u};
+                const uint32_t hd[5] = {n > 65535u || !last ? 0u : 1u, first & 255u, first >> 8, ~first & 255u, (~first >> 8) & 255u};
                 b = hd[k];
             } else if (k < 5u + first) {
-                b = (T[(k - 5u) >> 2] >> (8u * ((k - 5u) & 3u))) & 255u;
+                b = (T[(h + k - 5u) >> 2] >> (8u * ((h + k - 5u) & 3u))) & 255u;
             } else if (k < 10u + first) {        // (only with n = 65536: the second block holds one byte)
-                const uint32_t hd[5] = {1u, 1u, 0u, 0xFEu, 0xFFu};
+                const uint32_t hd[5] = {last ? 1u : 0u, 1u, 0u, 0xFEu, 0xFFu};
                 b = hd[k - 5u - first];
             } else {
-                b = (T[(k - 10u) >> 2] >> (8u * ((k - 10u) & 3u))) & 255u;
+                b = (T[(h + k - 10u) >> 2] >> (8u * ((h + k - 10u) & 3u))) & 255u;
             }
             slot[k] = (uint8_t)b;
         }
@@ -656,13 +724,13 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     }
 }
 
-size_t lds_bytes(uint32_t tile, int level) {
+size_t lds_bytes(uint32_t tile, int level) {     // (with a history: of tile + hist, the region's most)
     const uint32_t held = (tile + 3u) & ~3u;
     return offsetof(Lds, tile) + held + 16u + (level == 2 ? 2u * (held < kLinks ? held : kLinks) : 0u);
 }
 
-template <int kLevel>
-int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride, uint32_t *out_len,
+template <int kLevel, bool kHist>
+int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, uint8_t *dst, uint32_t stride, uint32_t *out_len,
            uint32_t *crc, void *scratch, void *stream) {
     if (!tile || tile > kTileMax) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: tile must be 1..65536");
     if (stride < FC2_DEFLATE_TILE_BOUND(tile))
@@ -672,19 +740,20 @@ int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, ui
     if (((uintptr_t)scratch & 3u) != 0) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: scratch must be 4-byte aligned");
     const uint64_t tiles = (n_bytes + tile - 1) / tile;
     if (tiles > 0x7FFFFFFFull) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: too many tiles for one launch");
-    // the kernel's LDS (over the 64 KiB a kernel gets unasked, for the larger tiles): once per device and level
+    // the kernel's LDS (over the 64 KiB a kernel gets unasked, for the larger tiles): once per device and instantiation
     static std::atomic<uint64_t> reserved{0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: no current device");
     const uint64_t bit = 1ull << (dev & 63);
     if (!(reserved.load() & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel<kLevel>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel<kLevel, kHist>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kTileMax, kLevel)) != hipSuccess)
             return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: cannot reserve the kernel's LDS");
         reserved |= bit;
     }
-    hipLaunchKernelGGL(deflate_kernel<kLevel>, dim3((uint32_t)tiles), dim3(64), lds_bytes(tile, kLevel), (hipStream_t)stream,
-                       src, n_bytes, tile, dst, stride, out_len, crc, static_cast<uint32_t *>(scratch));
+    hipLaunchKernelGGL((deflate_kernel<kLevel, kHist>), dim3((uint32_t)tiles), dim3(64), lds_bytes(tile + hist, kLevel),
+                       (hipStream_t)stream, src, n_bytes, tile, dst, stride, out_len, crc, static_cast<uint32_t *>(scratch),
+                       hist);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_deflate_launch: ") + hipGetErrorString(e));
 }
@@ -699,12 +768,23 @@ extern "C" uint64_t fc2_deflate_scratch_bytes(uint64_t n_bytes, uint32_t tile) {
 
 extern "C" int fc2_deflate_launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride,
                                   uint32_t *out_len, uint32_t *crc, void *scratch, void *stream) {
-    return launch<1>(src, n_bytes, tile, dst, stride, out_len, crc, scratch, stream);
+    return launch<1, false>(src, n_bytes, tile, 0, dst, stride, out_len, crc, scratch, stream);
 }
 
 extern "C" int fc2_deflate_launch_level(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride,
                                         uint32_t *out_len, uint32_t *crc, void *scratch, void *stream, int level) {
-    if (level == 1) return launch<1>(src, n_bytes, tile, dst, stride, out_len, crc, scratch, stream);
-    if (level == 2) return launch<2>(src, n_bytes, tile, dst, stride, out_len, crc, scratch, stream);
+    if (level == 1) return launch<1, false>(src, n_bytes, tile, 0, dst, stride, out_len, crc, scratch, stream);
+    if (level == 2) return launch<2, false>(src, n_bytes, tile, 0, dst, stride, out_len, crc, scratch, stream);
     return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_level: level is 1 or 2");
+}
+
+extern "C" int fc2_deflate_launch_hist(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, uint8_t *dst,
+                                       uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch, void *stream,
+                                       int level) {
+    if (level != 1 && level != 2) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_hist: level is 1 or 2");
+    if (!tile || tile > kTileMax || hist > kMaxDist || tile + hist > kTileMax)
+        return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_hist: tile must be 1..65536, hist 0..32768, tile + hist <= 65536");
+    if (!hist) return fc2_deflate_launch_level(src, n_bytes, tile, dst, stride, out_len, crc, scratch, stream, level);
+    if (level == 1) return launch<1, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream);
+    return launch<2, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream);
 }

@@ -23,8 +23,11 @@ constexpr double kDefaultTimeout = 60.0;       // seconds a wait for the device 
 
 // pieces of at most max_piece bytes in tiles of `tile` bytes (1..65536), every wait for the device
 // at most timeout_s seconds (<= 0: kDefaultTimeout), compressed at `level` (1 or 2:
-// fc2_deflate_launch_level); nullptr and err on failure
-Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, std::string &err);
+// fc2_deflate_launch_level); nullptr and err on failure.  hist > 0 (at most 32768, tile + hist <= 65536): a piece
+// is one launch of fc2_deflate_launch_hist -- every tile but the piece's first has the `hist` bytes before it as
+// its window -- and becomes one gzip member (fc2_gzmember_impl.h) instead of one per tile; pieces stay
+// independent of each other
+Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err);
 // frees everything; a device that timed out is not waited for (its buffers are left to the process's end)
 void gpu_close(Gpu *g);
 size_t gpu_max_piece(const Gpu *g);
@@ -35,8 +38,8 @@ bool gpu_submit(Gpu *g, int slot, const char *data, size_t n, std::string &err);
 enum Wait { DONE = 0, FAILED = 1, TIMED_OUT = 2 };
 // waits for the slot's piece, at most gpu_open's timeout_s seconds; the slot is idle afterwards
 Wait gpu_wait(Gpu *g, int slot, std::string &err);
-// after DONE: the bytes of the piece's gzip members (0: the kernel gave a tile up, the CPU must
-// compress the piece), and the members written to dst (that many bytes)
+// after DONE: the bytes of the piece's gzip members -- one per tile, or with a history one in all -- (0: the
+// kernel gave a tile up, the CPU must compress the piece), and the members written to dst (that many bytes)
 size_t gpu_members_size(const Gpu *g, int slot);
 void gpu_members_write(const Gpu *g, int slot, char *dst);
 

@@ -15,6 +15,7 @@
 #include "fc2_cpuacct.h"
 #include "fc2_deflate.h"
 #include "fc2_deflate_gpu.h"
+#include "fc2_gzmember_impl.h"
 
 namespace fc2 {
 namespace dgz {
@@ -40,6 +41,7 @@ struct Gpu {
     size_t max_piece = 0;
     double timeout_s = kDefaultTimeout;
     int level = 1;
+    uint32_t hist = 0;                         // > 0: fc2_deflate_launch_hist, and a piece is one member
     bool hung = false;                         // a wait timed out: the device is not touched again
     Slot slot[kSlots];
 };
@@ -50,9 +52,9 @@ static bool hip_ok(hipError_t e, const char *what, std::string &err) {
     return false;
 }
 
-Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, std::string &err) {
-    if (!tile || tile > 65536 || !max_piece || device < 0 || level < 1 || level > 2) {
-        err = "GPU gzip: bad tile, piece size, device or level";
+Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err) {
+    if (!tile || tile > 65536 || !max_piece || device < 0 || level < 1 || level > 2 || hist > 32768 || tile + hist > 65536) {
+        err = "GPU gzip: bad tile, history, piece size, device or level";
         return nullptr;
     }
     Gpu *g = new Gpu();
@@ -62,6 +64,7 @@ Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int
     g->max_piece = max_piece;
     g->timeout_s = timeout_s > 0 ? timeout_s : kDefaultTimeout;
     g->level = level;
+    g->hist = hist;
     g->max_tiles = (uint32_t)((max_piece + tile - 1) / tile);
     const size_t dst = (size_t)g->max_tiles * g->stride, meta = (size_t)g->max_tiles * 2 * sizeof(uint32_t);
     bool ok = hip_ok(hipSetDevice(device), "hipSetDevice", err);
@@ -128,8 +131,8 @@ bool gpu_submit(Gpu *g, int k, const char *data, size_t n, std::string &err) {
     s.busy = true;
     const bool ok =
         hip_ok(hipMemcpyAsync(s.d_src, s.h_src, n, hipMemcpyHostToDevice, s.stream), "upload", err) &&
-        (fc2_deflate_launch_level(s.d_src, n, g->tile, s.d_dst, g->stride, s.d_meta, s.d_meta + g->max_tiles, s.d_scratch,
-                                  s.stream, g->level) == FC2_OK || ((err = "GPU gzip: launch failed"), false)) &&
+        (fc2_deflate_launch_hist(s.d_src, n, g->tile, g->hist, s.d_dst, g->stride, s.d_meta, s.d_meta + g->max_tiles,
+                                 s.d_scratch, s.stream, g->level) == FC2_OK || ((err = "GPU gzip: launch failed"), false)) &&
         hip_ok(hipMemcpyAsync(s.h_dst, s.d_dst, (size_t)s.tiles * g->stride, hipMemcpyDeviceToHost, s.stream), "download", err) &&
         hip_ok(hipMemcpyAsync(s.h_meta, s.d_meta, s.tiles * w, hipMemcpyDeviceToHost, s.stream), "download", err) &&
         hip_ok(hipMemcpyAsync(s.h_meta + g->max_tiles, s.d_meta + g->max_tiles, s.tiles * w, hipMemcpyDeviceToHost, s.stream),
@@ -184,6 +187,7 @@ Wait gpu_wait(Gpu *g, int k, std::string &err) {
 
 size_t gpu_members_size(const Gpu *g, int k) {
     const Slot &s = g->slot[k];
+    if (g->hist) return (size_t)gzm::member_size(s.h_meta, s.tiles, s.n, g->tile);   // one member (fc2_gzmember_impl.h)
     size_t total = 0;
     for (uint32_t i = 0; i < s.tiles; ++i) {
         const uint32_t len = s.h_meta[i];
@@ -197,6 +201,10 @@ void gpu_members_write(const Gpu *g, int k, char *dst) {
     static const uint8_t head[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
     const Slot &s = g->slot[k];
     uint8_t *d = reinterpret_cast<uint8_t *>(dst);
+    if (g->hist) {
+        gzm::member_write(s.h_dst, g->stride, s.h_meta, s.h_meta + g->max_tiles, s.tiles, s.n, g->tile, d);
+        return;
+    }
     for (uint32_t i = 0; i < s.tiles; ++i) {
         const uint32_t len = s.h_meta[i], crc = s.h_meta[g->max_tiles + i];
         const uint64_t at = (uint64_t)i * g->tile;
@@ -226,8 +234,14 @@ extern "C" int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t til
 
 extern "C" int fc2_gpu_gzip_level(int device, const void *in, uint64_t n, uint32_t tile, int level, void *out, uint64_t cap,
                                   uint64_t *out_n) {
+    return fc2_gpu_gzip_hist(device, in, n, tile, 0, level, out, cap, out_n);
+}
+
+extern "C" int fc2_gpu_gzip_hist(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, int level, void *out,
+                                 uint64_t cap, uint64_t *out_n) {
     using namespace fc2;
-    if (!tile || tile > 65536 || device < 0 || !out || !out_n || (!in && n) || level < 1 || level > 2)
+    if (!tile || tile > 65536 || device < 0 || !out || !out_n || (!in && n) || level < 1 || level > 2 || hist > 32768 ||
+        tile + hist > 65536)
         return fc2::fail(FC2_E_PARAM, "fc2_gpu_gzip: bad arguments");
     *out_n = 0;
     char *o = static_cast<char *>(out);
@@ -242,7 +256,7 @@ extern "C" int fc2_gpu_gzip_level(int device, const void *in, uint64_t n, uint32
     }
     const size_t piece = size_t(4) << 20;
     std::string err;
-    dgz::Gpu *g = dgz::gpu_open(device, piece, tile, 0, level, err);
+    dgz::Gpu *g = dgz::gpu_open(device, piece, tile, 0, level, hist, err);
     if (!g) return fc2::fail(FC2_E_HIP, "fc2_gpu_gzip: " + err);
     const char *src = static_cast<const char *>(in);
     const uint64_t pieces = (n + piece - 1) / piece;

@@ -6,7 +6,8 @@
 // In device mode (set_device) a piece is compressed on the GPU instead (fc2_deflate.hip through
 // fc2_deflate_gpu.h): it goes up when it is submitted, up to four pieces are in flight, and when its turn to
 // be written comes its tiles are wrapped as gzip members here -- one per tile, so a piece is several
-// members.  The workers stay: they compress whatever the device path hands back (a piece whose
+// members; with a history (set_device's hist > 0: a tile may refer to the bytes of the piece before it) a piece is
+// one member, as a piece from the workers is.  The workers stay: they compress whatever the device path hands back (a piece whose
 // launch, copy or kernel failed, and every piece from then on) and the empty member of an empty file.
 #pragma once
 #include <stdio.h>
@@ -48,11 +49,12 @@ class GzPieces {
     }
 
     // device mode: pieces are compressed on GPU `device` from now on, in tiles of `tile` bytes, waiting
-    // at most timeout_s seconds for the device, at the compressor's `level` (call right after open()); false
-    // and err if the device's buffers cannot be made (the file then stays on the CPU)
-    bool set_device(int device, uint32_t tile, double timeout_s, int level, std::string &err) {
+    // at most timeout_s seconds for the device, at the compressor's `level`, every tile with the `hist` bytes of
+    // its piece before it as its window (0: none) (call right after open()); false and err if tile + hist is
+    // over 65536 or the device's buffers cannot be made (the file then stays on the CPU)
+    bool set_device(int device, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err) {
         if (!f_ || gpu_ || wrote_any_) { err = "GPU gzip: set the device once, after open and before any text"; return false; }
-        gpu_ = dgz::gpu_open(device, 2 * piece_, tile ? tile : dgz::kDefaultTile, timeout_s, level, err);   // (append_owned: up to two pieces long)
+        gpu_ = dgz::gpu_open(device, 2 * piece_, tile ? tile : dgz::kDefaultTile, timeout_s, level, hist, err);   // (append_owned: up to two pieces long)
         device_mode_ = gpu_ != nullptr;
         return device_mode_;
     }

@@ -74,7 +74,8 @@ class NativeCaller:
                  write_multi=True, genome_dummy=False, known_circ: str = "", known_lin: str = "",
                  bam_out: str = "", reads_gz=None, inflate_device=None, inflate_after: int = 0,
                  gzip_device=None, gzip_tile: int = 0, gzip_timeout_s: float = 0.0, gpu_walk: bool = True,
-                 gpu_digest: bool = False, gpu_group: int = 0, bam_device=None, gzip_level: int = 1):
+                 gpu_digest: bool = False, gpu_group: int = 0, bam_device=None, gzip_level: int = 1,
+                 gzip_history: int = 0):
         o = copts
         # the strings must outlive the handle's open call (fc2_caller_open copies them)
         self._keep = [o.name.encode(), known_circ.encode() if known_circ else None,
@@ -104,6 +105,7 @@ class NativeCaller:
         self.gzip_tile = gzip_tile             # ... in tiles of this many bytes (0: 32768), each a gzip member
         self.gzip_timeout_s = gzip_timeout_s   # ... waiting at most this long for the device (0: 60 s)
         self.gzip_level = int(gzip_level)      # ... at this level of the GPU compressor (1 or 2)
+        self.gzip_history = int(gzip_history)  # ... a tile referring to this many bytes before it (0: none; a piece is then one member)
         self.opened = False
         self.format = None           # "sam" | "bam", detected from the bytes (open)
         self.loop_profile = {}       # seconds per stage of the last run (two-thread loop)
@@ -136,6 +138,8 @@ class NativeCaller:
                 N.check(L.fc2_caller_set_reads_gz_device_tuning(self.h, int(self.gzip_tile), float(self.gzip_timeout_s)))
                 if self.gzip_level != 1:
                     N.check(L.fc2_caller_set_reads_gz_device_level(self.h, self.gzip_level))
+                if self.gzip_history:
+                    N.check(L.fc2_caller_set_reads_gz_device_history(self.h, self.gzip_history))
                 N.check(L.fc2_caller_set_reads_gz_device(self.h, int(self.gzip_device)))
         n_ref = L.fc2_ingest_n_refs(ing)
         self.refs = [L.fc2_ingest_ref_name(ing, t).decode("latin-1") for t in range(n_ref)]

@@ -131,6 +131,13 @@ int fc2_caller_set_reads_gz_device_tuning(fc2_caller *h, uint32_t tile, double t
  * mode set afterwards with fc2_caller_set_reads_gz_device; FC2_E_PARAM for another level or a call after it.
  * The command line passes FC2_GPU_GZIP_LEVEL here. */
 int fc2_caller_set_reads_gz_device_level(fc2_caller *h, int level);
+/* This handle's history on the device (bytes, 0..32768; 0, the default: none), for the device mode set afterwards
+ * with fc2_caller_set_reads_gz_device: every tile of a piece but its first has the `hist` bytes before it as its
+ * window (fc2_deflate_launch_hist), and a piece is one gzip member instead of one per tile.  FC2_E_PARAM for more
+ * than 32768 or a call after fc2_caller_set_reads_gz_device; a tile and history of more than 65536 bytes together
+ * are refused by fc2_caller_set_reads_gz_device itself (FC2_E_PARAM), which then leaves the CPU writer in place.
+ * The command line passes FC2_GPU_GZIP_HISTORY here. */
+int fc2_caller_set_reads_gz_device_history(fc2_caller *h, uint32_t hist);
 /* pieces the device compressed, and pieces of the device mode the CPU compressed, so far (0, 0 without it) */
 int fc2_caller_reads_gz_counts(const fc2_caller *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces);
 
@@ -150,6 +157,14 @@ int fc2_deflate_launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint
  * same arguments, scratch and bound.  Any other level: FC2_E_PARAM, before the device is touched. */
 int fc2_deflate_launch_level(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint8_t *dst, uint32_t stride,
                              uint32_t *out_len, uint32_t *crc, void *scratch, void *stream, int level);
+/* fc2_deflate_launch_level with a history: the launch's n_bytes are one raw DEFLATE stream cut into tiles.  Tile i
+ * may refer to the min(hist, i * tile) input bytes before it (its window: nothing of another tile's output), and
+ * every tile's stream but the last ends on a byte boundary with BFINAL = 0, so the streams back to back, in
+ * order, are the stream of src[0, n_bytes); crc[i] stays the CRC-32 of tile i's own bytes.  tile 1..65536, hist
+ * 0..32768, tile + hist <= 65536, level 1 or 2: anything else is FC2_E_PARAM before the device is touched.
+ * hist = 0 is fc2_deflate_launch_level byte for byte (every tile a stream of its own).  Same scratch and bound. */
+int fc2_deflate_launch_hist(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, uint8_t *dst,
+                            uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch, void *stream, int level);
 uint64_t fc2_deflate_scratch_bytes(uint64_t n_bytes, uint32_t tile);
 /* one buffer through the host path of spliced_reads.fastq.gz's device mode, for tests and other hosts: gzip
  * members (one per tile) of in[0, n) into out (cap bytes); FC2_E_RANGE if they do not fit. */
@@ -157,6 +172,10 @@ int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, void *ou
 /* fc2_gpu_gzip with the tiles compressed at `level` (1 or 2, fc2_deflate_launch_level; else FC2_E_PARAM) */
 int fc2_gpu_gzip_level(int device, const void *in, uint64_t n, uint32_t tile, int level, void *out, uint64_t cap,
                        uint64_t *out_n);
+/* fc2_gpu_gzip_level with a history of `hist` bytes (fc2_deflate_launch_hist's rules): every piece of 4 MiB is one
+ * gzip member, its tiles' streams back to back (csrc/fc2_gzmember_impl.h).  hist = 0: fc2_gpu_gzip_level's bytes. */
+int fc2_gpu_gzip_hist(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, int level, void *out,
+                      uint64_t cap, uint64_t *out_n);
 uint64_t fc2_gpu_gzip_bound(uint64_t n, uint32_t tile);
 
 /* ---- BGZF output on the GPU (csrc/fc2_bgzf_out.hip; the rule: csrc/fc2_bgzf_frame_impl.h) ---- */

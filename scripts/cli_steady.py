@@ -24,7 +24,8 @@ usage: python scripts/cli_steady.py [--sizes 2000000,20000000] [--threads 4,8,16
 library) instead of one junction each (the junction tables then stay small).
 -B: every run writes spliced_alignments.bam too (the CLI's -B; --variants FC2_GPU_BAM=1 compresses it on the GPU).
 --variants: each comma-separated entry is a run of its own; an entry may hold several settings joined by "+"
-(FC2_GPU_BAM=1+FC2_GPU_BAM_LEVEL=2).  Mind the comma: "FC2_GPU_BAM=1,FC2_GPU_BAM_LEVEL=2" is two runs, the
+(FC2_GPU_BAM=1+FC2_GPU_BAM_LEVEL=2, FC2_GPU_GZIP=1+FC2_GPU_GZIP_LEVEL=2+FC2_GPU_GZIP_HISTORY=32768; a record's
+"history" is what run.log then reports).  Mind the comma: "FC2_GPU_BAM=1,FC2_GPU_BAM_LEVEL=2" is two runs, the
 second with the level alone, which the command line does not read without FC2_GPU_BAM=1; the comma kept its
 meaning so that earlier command lines measure what they measured.  Every record carries the sizes of the two
 compressed output files.
@@ -144,6 +145,7 @@ def run_cli(fa, bam, out, threads, extra=(), timeout=900, timing=False, by_path=
              if os.path.exists(os.path.join(out, f))}
     return {
         "output_bytes": sizes, "levels": {k: int(v) for k, v in phases.items() if k.endswith("_gpu_level")},
+        "history": {k: int(v) for k, v in phases.items() if k.endswith("_gpu_history")},
         "threads": threads, "cpus": len(cpus) if cpus else None, "process_wall_s": round(wall, 3),
         "reads": reads, "spans": spans,
         "loop_s": loop_s, "genome_wait_s": phases.get("genome_wait_s"),

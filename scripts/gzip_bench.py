@@ -5,10 +5,12 @@ HIP events on the launch stream; with both copies (fc2_gpu_gzip: pinned staging,
 download, members assembled) on the wall clock; every tile's stream checked with zlib.  The CPU legs
 are libdeflate level 1 (the default writer; fc2_deflate.h) and zlib level 1 on one core over the same
 bytes, and zlib level 6 over each tile alone (what a BGZF writer at its default makes of the same cuts).
---level 2 runs the compressor's second level (fc2_deflate_launch_level).  One JSON line.  Measurement
-infrastructure (not part of the product).
+--level 2 runs the compressor's second level (fc2_deflate_launch_level).  --hist H gives every tile the H
+bytes before it in its launch as a window (fc2_deflate_launch_hist, fc2_gpu_gzip_hist): a launch is then one
+DEFLATE stream, checked whole -- the piece launches' streams are the ones inflated -- and zlib level 6's
+figure stays that of tiles cut alone.  One JSON line.  Measurement infrastructure (not part of the product).
 
-usage: python scripts/gzip_bench.py [--reads N | --text FILE] [--tile T] [--piece P] [--reps R] [--level 1|2]
+usage: python scripts/gzip_bench.py [--reads N | --text FILE] [--tile T] [--piece P] [--reps R] [--level 1|2] [--hist H]
 """
 import argparse
 import ctypes
@@ -69,6 +71,7 @@ def main():
     ap.add_argument("--piece", type=int, default=4 << 20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--level", type=int, default=1, choices=[1, 2])
+    ap.add_argument("--hist", type=int, default=0)
     a = ap.parse_args()
     import torch
     from find_circ2_amd import _native as N
@@ -88,6 +91,11 @@ def main():
 
     def launch(t0, t1):
         b0, b1 = t0 * tile, min(n, t1 * tile)
+        if a.hist:
+            N.check(L.fc2_deflate_launch_hist(src.data_ptr() + b0, b1 - b0, tile, a.hist, dst.data_ptr() + t0 * stride,
+                                              stride, ln.data_ptr() + 4 * t0, cr.data_ptr() + 4 * t0,
+                                              scratch.data_ptr() + 4 * b0, ctypes.c_void_p(stream.cuda_stream), a.level))
+            return
         N.check(L.fc2_deflate_launch_level(src.data_ptr() + b0, b1 - b0, tile, dst.data_ptr() + t0 * stride, stride,
                                            ln.data_ptr() + 4 * t0, cr.data_ptr() + 4 * t0, scratch.data_ptr() + 4 * b0,
                                            ctypes.c_void_p(stream.cuda_stream), a.level))
@@ -109,13 +117,28 @@ def main():
         spread[step] = every
         return best
 
-    launch(0, tiles)
+    if a.hist:                                      # checked as the writer launches: a stream per piece
+        for t0 in range(0, tiles, per):
+            launch(t0, min(tiles, t0 + per))
+    else:
+        launch(0, tiles)
     torch.cuda.synchronize()
     lens = ln.cpu().numpy().view(np.uint32)
     crcs = cr.cpu().numpy().view(np.uint32)
     out = dst.cpu().numpy()
     bad = 0
-    for i in range(tiles):
+    for t0 in range(0, tiles if a.hist else 0, per):
+        t1 = min(tiles, t0 + per)
+        want = text[t0 * tile:t1 * tile]
+        z = zlib.decompressobj(-15)
+        try:
+            ok = z.decompress(b"".join(out[i * stride:i * stride + int(lens[i])].tobytes() for i in range(t0, t1))) == want \
+                and z.eof and not z.unused_data
+        except zlib.error:
+            ok = False
+        bad += (t1 - t0) if not ok else sum(int(crcs[i]) != zlib.crc32(text[i * tile:(i + 1) * tile]) for i in range(t0, t1))
+    stream_bytes = int(lens.sum())
+    for i in range(0 if a.hist else tiles):
         want = text[i * tile:(i + 1) * tile]
         z = zlib.decompressobj(-15)
         try:
@@ -131,7 +154,10 @@ def main():
     wall = None
     for _ in range(max(2, a.reps)):
         t0 = time.time()
-        N.check(L.fc2_gpu_gzip_level(0, text, n, tile, a.level, buf, cap, ctypes.byref(got)))
+        if a.hist:
+            N.check(L.fc2_gpu_gzip_hist(0, text, n, tile, a.hist, a.level, buf, cap, ctypes.byref(got)))
+        else:
+            N.check(L.fc2_gpu_gzip_level(0, text, n, tile, a.level, buf, cap, ctypes.byref(got)))
         s = time.time() - t0
         wall = s if wall is None else min(wall, s)
     host_ok = gzip.decompress(bytes(bytearray(buf)[:got.value])) == text
@@ -144,10 +170,10 @@ def main():
         c = zlib.compressobj(6, zlib.DEFLATED, -15)
         z6 += len(c.compress(text[b0:b0 + tile])) + len(c.flush())
     print(json.dumps({
-        "text_bytes": n, "level": a.level, "tile": tile, "tiles": tiles, "bad_tiles": int(bad), "host_path_ok": bool(host_ok),
-        "gpu_stream_bytes": int(lens.sum()), "gpu_gzip_bytes": int(got.value),
+        "text_bytes": n, "level": a.level, "tile": tile, "hist": a.hist, "tiles": tiles, "bad_tiles": int(bad), "host_path_ok": bool(host_ok),
+        "gpu_stream_bytes": stream_bytes, "gpu_gzip_bytes": int(got.value),
         "gpu_ratio": round(int(got.value) / n, 4),
-        "zlib6_per_tile_stream_bytes": z6, "gpu_over_zlib6_per_tile": round(int(lens.sum()) / z6, 4),
+        "zlib6_per_tile_stream_bytes": z6, "gpu_over_zlib6_per_tile": round(stream_bytes / z6, 4),
         "gpu_one_launch_ms_every": spread[tiles], "gpu_pieces_ms_every": spread[per],
         "gpu_one_launch_ms": round(ms_all, 3), "gpu_one_launch_GBps": round(n / ms_all / 1e6, 2),
         "gpu_piece_bytes": per * tile, "gpu_pieces_ms": round(ms_piece, 3), "gpu_pieces_GBps": round(n / ms_piece / 1e6, 2),
