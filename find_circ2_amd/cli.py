@@ -322,13 +322,25 @@ def _gzip_device(options):
 def _bam_device(options):
     """spliced_alignments.bam's records compressed on the GPU (DESIGN.md §5 "BGZF output on the device"): only
     with FC2_GPU_BAM=1, on the first of the run's devices, waiting at most FC2_GPU_BAM_TIMEOUT_S seconds (60)
-    for it, at the compressor's level 2 with FC2_GPU_BAM_LEVEL=2 (unset or anything else: level 1).  Unset, 0
-    or anything else: None, zlib compresses on the reading thread."""
+    for it, at the compressor's level 2 with FC2_GPU_BAM_LEVEL=2 (unset or anything else: level 1), every block
+    cut into tiles of FC2_GPU_BAM_TILE bytes (unset, empty or 0: the block is one tile) that see the
+    FC2_GPU_BAM_HISTORY bytes (0..32768; unset, empty or 0: none) of their block before them (DESIGN.md §5
+    "Tiles inside a BGZF block").  Unset, 0 or anything else: None, zlib compresses on the reading thread, and
+    neither of the two is read."""
     if os.environ.get("FC2_GPU_BAM") != "1":
         return None
     from .ctxpipe import device_index
     return dict(mode=1, device=device_index(options.device), timeout_s=float(os.environ.get("FC2_GPU_BAM_TIMEOUT_S") or 0),
-                level=2 if os.environ.get("FC2_GPU_BAM_LEVEL") == "2" else 1)
+                level=2 if os.environ.get("FC2_GPU_BAM_LEVEL") == "2" else 1,
+                tile=int(os.environ.get("FC2_GPU_BAM_TILE") or 0), hist=int(os.environ.get("FC2_GPU_BAM_HISTORY") or 0))
+
+
+def _bam_tiles_note(bam_device) -> str:
+    """run.log's note of a tile below the block (0xff00, the command line's) and of its history."""
+    tile, hist = (int(bam_device.get(k) or 0) for k in ("tile", "hist")) if bam_device else (0, 0)
+    if not 0 < tile < 0xff00:
+        return ""
+    return ", bam_gpu_tile=%d" % tile + (", bam_gpu_history=%d" % hist if hist > 0 else "")
 
 
 def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory, genome, bam_path="",
@@ -416,7 +428,7 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                 startup.update(zip(("bam_gpu_pieces", "bam_cpu_pieces"), nc.bam_out_pieces))
             levels = (", gzip_gpu_level=2" if nc.gzip_device is not None and nc.gzip_level == 2 else "") + \
                 (", gzip_gpu_history=%d" % nc.gzip_history if nc.gzip_device is not None and nc.gzip_history > 0 else "") + \
-                (", bam_gpu_level=2" if nc.bam_device and nc.bam_device.get("level") == 2 else "")
+                (", bam_gpu_level=2" if nc.bam_device and nc.bam_device.get("level") == 2 else "") + _bam_tiles_note(nc.bam_device)
             logger.info("process phases: " + ", ".join("%s=%.3f" % kv for kv in startup.items()) + levels +
                         ", process_age_s=%.3f, numpy_loaded=%d, torch_loaded=%d"
                         % (process_age(), "numpy" in sys.modules, "torch" in sys.modules))

@@ -86,6 +86,7 @@ struct Writer {
     static constexpr uint64_t kNever = ~0ull;
     int mode = 0;
     uint32_t block = 0, stride = 0;
+    uint32_t tile = 0, hist = 0;           // tile > 0: a block is cut into tiles (set_device), the slots are the tiles'
     size_t piece_bytes = 0;
     bgz::Gpu *gpu = nullptr;
     bool timed_out = false;
@@ -105,6 +106,7 @@ struct Writer {
     // what the device does with a piece, on the host: every tile raw-deflated by zlib level 1 into its slot
     // (0xFFFFFFFF: it does not fit the slot), then fc2_bgzf_frame_host
     bool model_submit(int k) {
+        if (tile) return model_submit_tiles(k);
         Model &m = model[k];
         const std::string &src = in[k];
         const uint32_t tiles = (uint32_t)((src.size() + block - 1) / block);
@@ -128,6 +130,47 @@ struct Writer {
         deflateEnd(&z1);
         return fc2_bgzf_frame_host(m.slots.data(), stride, m.len.data(), m.crc.data(), tiles, src.size(), block,
                                    m.framed.data(), m.off.data(), &m.total) == FC2_OK;
+    }
+
+    // the same for blocks cut into tiles (fc2_deflate_launch_groups, fc2_bgzf_frame_groups_host): a block is one
+    // raw stream from zlib level 1, flushed to a byte boundary (Z_SYNC_FLUSH: the empty stored block the device
+    // writes too) at every tile's end but the block's last, which finishes it; each tile's part into its slot.
+    // zlib's window reaches back 32 KiB inside the block whatever `hist` is: the model stands for the stream
+    // form, the tables and the framing, not for the device's bytes
+    bool model_submit_tiles(int k) {
+        Model &m = model[k];
+        const std::string &src = in[k];
+        const uint32_t tpg = (block - 1) / tile + 1, blocks = (uint32_t)((src.size() + block - 1) / block);
+        const uint32_t tiles = (uint32_t)fc2_deflate_group_tiles(src.size(), block, tile);
+        m.slots.assign((size_t)tiles * stride, 0);
+        m.len.assign(tiles, 0);
+        m.crc.assign(tiles, 0);
+        m.off.assign(blocks + 1, 0);
+        m.framed.assign((size_t)blocks * kBlockMax, 0);
+        z_stream z1{};
+        if (deflateInit2(&z1, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        for (uint32_t g = 0; g < blocks; ++g) {
+            const size_t g0 = (size_t)g * block, gn = std::min<size_t>(block, src.size() - g0);
+            deflateReset(&z1);
+            bool fits = true;
+            for (size_t t0 = 0; t0 < gn; t0 += tile) {
+                const size_t n = std::min<size_t>(tile, gn - t0), i = (size_t)g * tpg + t0 / tile;
+                const bool last = t0 + n == gn;
+                z1.next_in = (Bytef *)(src.data() + g0 + t0);
+                z1.avail_in = (uInt)n;
+                z1.next_out = m.slots.data() + i * stride;
+                z1.avail_out = stride;
+                if (fits) {
+                    const int rc = deflate(&z1, last ? Z_FINISH : Z_SYNC_FLUSH);
+                    fits = last ? rc == Z_STREAM_END : (rc == Z_OK && z1.avail_out != 0);
+                }
+                m.len[i] = fits ? stride - z1.avail_out : 0xFFFFFFFFu;      // (0xFFFFFFFF: it does not fit the slot)
+                m.crc[i] = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)(src.data() + g0 + t0), (uInt)n);
+            }
+        }
+        deflateEnd(&z1);
+        return fc2_bgzf_frame_groups_host(m.slots.data(), stride, m.len.data(), m.crc.data(), tiles, src.size(), block, tile,
+                                          m.framed.data(), m.off.data(), &m.total) == FC2_OK;
     }
 
     // the piece in pend into the next slot (a slot in use: its piece written first)
@@ -425,7 +468,7 @@ bool encode_sam(const char *line, const char *end, const std::unordered_map<std:
 bool device_set(const Writer *w) { return w && w->mode != 0; }
 
 bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level,
-                std::string &err) {
+                uint32_t tile, uint32_t hist, std::string &err) {
     if (!block) block = bgz::kDefaultBlock;
     if (!piece_blocks) piece_blocks = bgz::kDefaultPieceBlocks;
     if (!w || mode < 0 || mode > 2 || block > kBlockIn || piece_blocks > bgz::kMaxPieceBlocks || timeout_s < 0 ||
@@ -438,10 +481,17 @@ bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_
         return false;
     }
     if (!mode) return true;
-    if (mode == 1 && !(w->gpu = bgz::gpu_open(device, block, piece_blocks, timeout_s, level, err))) return false;
+    if (tile >= block) tile = 0;                // (a block is one tile)
+    if (tile && (hist > 32768u || tile + hist > 65536u || (block - 1) / tile + 1 > 16)) {
+        err = "at most 16 tiles a block, a history of at most 32768 bytes, tile and history at most 65536 together";
+        return false;
+    }
+    if (mode == 1 && !(w->gpu = bgz::gpu_open(device, block, piece_blocks, timeout_s, level, tile, hist, err))) return false;
     w->mode = mode;
     w->block = block;
-    w->stride = (FC2_DEFLATE_TILE_BOUND(block) + 15u) & ~15u;
+    w->tile = tile;
+    w->hist = tile ? hist : 0;
+    w->stride = (FC2_DEFLATE_TILE_BOUND(tile ? tile : block) + 15u) & ~15u;
     w->piece_bytes = (size_t)block * piece_blocks;
     return true;
 }

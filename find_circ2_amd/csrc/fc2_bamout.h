@@ -39,8 +39,12 @@ bool write_bulk(Writer *w, const char *p, size_t n, int threads);
 // is waited for and written before the slot is reused: the pieces reach the file in order, from the calling
 // thread.  A piece the device fails on or hands back, and every later one, is compressed by zlib as above.  A
 // device that does not answer within timeout_s seconds fails the call that waited and close_writer.
+// tile (0 or >= block: none) cuts every block into tiles of that many bytes, each with up to `hist` bytes of its
+// block before it as history (fc2_deflate_launch_groups, fc2_bgzf_frame_groups_launch; mode 2: zlib flushed
+// at the tiles' ends and fc2_bgzf_frame_groups_host); more than 16 tiles a block, hist over 32768 or tile + hist
+// over 65536 are refused.
 bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level,
-                std::string &err);
+                uint32_t tile, uint32_t hist, std::string &err);
 bool device_set(const Writer *w);              // set_device has put the writer into mode 1 or 2
 // pieces written from the device (or the host model), and pieces of the device mode zlib compressed, so far
 void device_counts(const Writer *w, uint64_t &gpu_pieces, uint64_t &cpu_pieces);

@@ -24,8 +24,13 @@ constexpr double kDefaultTimeout = 60.0;       // seconds a wait for the device 
 
 // pieces of at most piece_blocks (1..kMaxPieceBlocks) blocks of `block` (1..0xff00) input bytes, every wait
 // for the device at most timeout_s seconds (<= 0: kDefaultTimeout), compressed at `level` (1 or 2:
-// fc2_deflate_launch_level); nullptr and err on failure
-Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level, std::string &err);
+// fc2_deflate_launch_level); nullptr and err on failure.  tile = 0 or tile >= block: a block is one tile, as
+// above.  Otherwise every block is cut into ceil(block / tile) <= 16 tiles, tile k of a block having the
+// min(hist, k * tile) bytes of its block before it as history (hist 0..32768, tile + hist <= 65536):
+// fc2_deflate_launch_groups fills piece_blocks * ceil(block / tile) slots and fc2_bgzf_frame_groups_launch packs
+// each block's streams, its combined CRC-32 and ISIZE into one BGZF block; the rest is the same
+Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level, uint32_t tile, uint32_t hist,
+              std::string &err);
 // frees everything; a device that timed out is not waited for (its buffers are left to the process's end)
 void gpu_close(Gpu *g);
 // a wait timed out: the device is not touched again, every later call fails

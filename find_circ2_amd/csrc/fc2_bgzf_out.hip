@@ -1,6 +1,8 @@
 // fc2_bgzf_out.hip -- BGZF output on the GPU: bgzf_frame_kernel packs the slots deflate_kernel
 // (fc2_deflate.hip) filled into the finished block stream (the rule: fc2_bgzf_frame_impl.h), the slots of
-// the device writer (fc2_bgzf_gpu.h), and fc2_gpu_bgzf (one buffer through the same path).
+// the device writer (fc2_bgzf_gpu.h), and fc2_gpu_bgzf (one buffer through the same path).  With tiles inside a
+// block (fc2_deflate_launch_groups) bgzf_groups_scan_kernel and bgzf_groups_kernel do the packing: a block is its
+// tiles' streams back to back, its CRC-32 combined from theirs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -156,6 +158,174 @@ extern "C" int fc2_bgzf_frame_host(const uint8_t *slots, uint32_t stride, const 
     return FC2_OK;
 }
 
+// ---- groups: a block of several tiles ----------------------------------------------------------------
+
+namespace {
+
+// A piece of 1024 blocks of 16 tiles has 16384 out_len entries: if every workgroup summed all of them for its
+// offset, as bgzf_frame_kernel does with its 64, a piece would read 16 M entries where 16 K are needed.  So the
+// offsets come from one workgroup that runs first, on the same stream: thread t sums the blocks of its share of
+// the groups (each group's tiles checked with tile_ok, each block against 65536), the shares' sums are scanned,
+// and off[0 .. n_groups] and total are written -- zeros if anything was invalid.  bgzf_groups_kernel then reads
+// only off[g], total (0: the piece stays unwritten) and its own group's entries; no workgroup waits for another.
+__global__ __launch_bounds__(kFrameThreads) void bgzf_groups_scan_kernel(const uint32_t *__restrict__ out_len,
+                                                                         uint32_t n_groups, uint64_t n_bytes,
+                                                                         uint32_t group, uint32_t tile,
+                                                                         uint32_t *__restrict__ off,
+                                                                         uint32_t *__restrict__ total) {
+    __shared__ uint32_t sum[kFrameThreads];
+    __shared__ uint32_t bad[kFrameThreads];
+    const uint32_t t = threadIdx.x, tpg = tiles_per_group(group, tile);
+    const uint32_t per = (n_groups + kFrameThreads - 1) / kFrameThreads;
+    const uint32_t g0 = min(t * per, n_groups), g1 = min(g0 + per, n_groups);
+    uint32_t all = 0, invalid = 0;
+    for (uint32_t g = g0; g < g1; ++g) {
+        const uint32_t cnt = group_tile_count(group_bytes(g, n_groups, n_bytes, group), tile);
+        uint32_t b = kOverhead;
+        for (uint32_t k = 0; k < cnt; ++k) {
+            const uint32_t len = out_len[g * tpg + k];
+            if (tile_ok(len, tile)) b += len;   // (at most 16 * 65552: no overflow)
+            else invalid = 1;
+        }
+        if (b > kBlockMax) invalid = 1;
+        all += b;
+    }
+    sum[t] = all;
+    bad[t] = invalid;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t run = 0, any = 0;
+        for (uint32_t k = 0; k < kFrameThreads; ++k) {
+            const uint32_t v = sum[k];
+            sum[k] = run;
+            run += v;
+            any |= bad[k];
+        }
+        bad[0] = any;
+        off[n_groups] = any ? 0 : run;
+        *total = any ? 0 : run;
+    }
+    __syncthreads();
+    const bool valid = bad[0] == 0;
+    uint32_t run = sum[t];
+    for (uint32_t g = g0; g < g1; ++g) {
+        off[g] = valid ? run : 0;
+        if (!valid) continue;
+        const uint32_t cnt = group_tile_count(group_bytes(g, n_groups, n_bytes, group), tile);
+        run += kOverhead;
+        for (uint32_t k = 0; k < cnt; ++k) run += out_len[g * tpg + k];
+    }
+}
+
+// One workgroup per block, after bgzf_groups_scan_kernel.  The group's (at most 16) stream lengths and their
+// running sum are put into LDS; thread k < cnt also brings tile k's CRC to the group's end (crc_shift by the
+// input bytes behind the tile), and the XOR of those is the group's CRC -- crc_append unrolled, no input read.
+// Each tile's stream is copied as in bgzf_frame_kernel: its slot is 16-byte aligned, its destination -- where
+// the previous tile's stream ended -- is not, so the lead up to the destination's next 16-byte boundary and the
+// tail behind its last one go byte by byte and the rest as whole uint4 stores.  Every store lies in
+// [out + off[g], out + off[g + 1]) of a valid piece; every load in a slot, a valid out_len being at most stride.
+__global__ __launch_bounds__(kFrameThreads) void bgzf_groups_kernel(const uint8_t *__restrict__ slots, uint32_t stride,
+                                                                    const uint32_t *__restrict__ out_len,
+                                                                    const uint32_t *__restrict__ crc, uint32_t n_groups,
+                                                                    uint64_t n_bytes, uint32_t group, uint32_t tile,
+                                                                    uint8_t *__restrict__ out,
+                                                                    const uint32_t *__restrict__ off,
+                                                                    const uint32_t *__restrict__ total) {
+    __shared__ uint32_t lens[kTilesPerGroupMax], at[kTilesPerGroupMax + 1], part[kTilesPerGroupMax];
+    const uint32_t g = blockIdx.x, t = threadIdx.x;
+    if (g >= n_groups || *total == 0) return;   // (uniform)
+    const uint32_t tpg = tiles_per_group(group, tile), first = g * tpg;
+    const uint32_t gbytes = group_bytes(g, n_groups, n_bytes, group), cnt = group_tile_count(gbytes, tile);
+    if (t < cnt) {
+        lens[t] = out_len[first + t];
+        const uint32_t behind = gbytes - (t * tile + group_tile_bytes(t, gbytes, tile));
+        part[t] = crc_shift(crc[first + t], behind);
+    }
+    __syncthreads();
+    if (t == 0) {
+        uint32_t run = 0;
+        for (uint32_t k = 0; k < cnt; ++k) {
+            at[k] = run;
+            run += lens[k];
+        }
+        at[cnt] = run;
+    }
+    __syncthreads();
+    const uint32_t len = at[cnt], bsize = block_bytes(len);
+    uint8_t *const b = out + off[g];
+    if (t < kHead) b[t] = head_byte(t, bsize);
+    else if (t >= 32 && t < 32 + kTail) {
+        uint32_t c = 0;
+        for (uint32_t k = 0; k < cnt; ++k) c ^= part[k];
+        b[kHead + len + (t - 32)] = tail_byte(t - 32, c, gbytes);
+    }
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const uint32_t n = lens[k];
+        const uint8_t *const s = slots + (uint64_t)(first + k) * stride;
+        const uint32_t *const w = reinterpret_cast<const uint32_t *>(s);
+        uint8_t *const d = b + kHead + at[k];
+        const uint32_t lead = min(n, (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u));
+        const uint32_t whole = (n - lead) / 16u;                // uint4 stores at d + lead + 16 * m
+        const uint32_t tail0 = lead + whole * 16u;
+        if (t < lead) d[t] = s[t];
+        if (t >= 64 && t < 64 + (n - tail0)) d[tail0 + (t - 64)] = s[tail0 + (t - 64)];    // (fewer than 16)
+        for (uint32_t m = t; m < whole; m += kFrameThreads) {
+            const uint32_t o = lead + m * 16u;
+            uint4 v;
+            v.x = slot_u32(w, o);
+            v.y = slot_u32(w, o + 4);
+            v.z = slot_u32(w, o + 8);
+            v.w = slot_u32(w, o + 12);
+            *reinterpret_cast<uint4 *>(d + o) = v;
+        }
+    }
+}
+
+int check_groups_args(const char *who, const void *slots, uint32_t stride, const void *out_len, const void *crc,
+                      uint32_t n_tiles, uint64_t n_bytes, uint32_t group, uint32_t tile, const void *out, const void *off,
+                      const void *total) {
+    const std::string w(who);
+    if (!slots || !out_len || !crc || !out || !off || !total) return fc2::fail(FC2_E_PARAM, w + ": null argument");
+    if (!groups_ok(n_tiles, n_bytes, group, tile))
+        return fc2::fail(FC2_E_PARAM, w + ": group must be 1..0xff00, tile 1..65536 with at most 16 tiles a group, at most "
+                                          "65535 groups, and n_tiles the tiles of n_bytes");
+    if (stride < FC2_DEFLATE_TILE_BOUND(tile)) return fc2::fail(FC2_E_PARAM, w + ": stride below FC2_DEFLATE_TILE_BOUND(tile)");
+    return FC2_OK;
+}
+
+}  // namespace
+
+extern "C" int fc2_bgzf_frame_groups_launch(const uint8_t *slots, uint32_t stride, const uint32_t *out_len,
+                                            const uint32_t *crc, uint32_t n_tiles, uint64_t n_bytes, uint32_t group,
+                                            uint32_t tile, uint8_t *out, uint32_t *off, uint32_t *total, void *stream) {
+    if (int rc = check_groups_args("fc2_bgzf_frame_groups_launch", slots, stride, out_len, crc, n_tiles, n_bytes, group, tile,
+                                   out, off, total))
+        return rc;
+    if (((uintptr_t)slots & 15u) || (stride & 15u))
+        return fc2::fail(FC2_E_PARAM, "fc2_bgzf_frame_groups_launch: the slots must lie on 16-byte boundaries");
+    const uint32_t n_groups = groups_of(n_bytes, group);
+    hipLaunchKernelGGL(bgzf_groups_scan_kernel, dim3(1), dim3(kFrameThreads), 0, (hipStream_t)stream, out_len, n_groups, n_bytes,
+                       group, tile, off, total);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(bgzf_groups_kernel, dim3(n_groups), dim3(kFrameThreads), 0, (hipStream_t)stream, slots, stride,
+                           out_len, crc, n_groups, n_bytes, group, tile, out, off, total);
+        e = hipGetLastError();
+    }
+    return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_bgzf_frame_groups_launch: ") + hipGetErrorString(e));
+}
+
+extern "C" int fc2_bgzf_frame_groups_host(const uint8_t *slots, uint32_t stride, const uint32_t *out_len, const uint32_t *crc,
+                                          uint32_t n_tiles, uint64_t n_bytes, uint32_t group, uint32_t tile, uint8_t *out,
+                                          uint32_t *off, uint32_t *total) {
+    if (total) *total = 0;
+    if (int rc = check_groups_args("fc2_bgzf_frame_groups_host", slots, stride, out_len, crc, n_tiles, n_bytes, group, tile, out,
+                                   off, total))
+        return rc;
+    frame_groups(slots, stride, out_len, crc, n_tiles, n_bytes, group, tile, out, off, total);
+    return FC2_OK;
+}
+
 // ---- the device writer's slots ---------------------------------------------------------------------
 
 namespace fc2 {
@@ -178,6 +348,7 @@ struct Gpu {
     size_t max_piece = 0, out_cap = 0;
     double timeout_s = kDefaultTimeout;
     int level = 1;                             // fc2_deflate_launch_level's
+    uint32_t tile = 0, hist = 0, tpg = 1;      // tile > 0: blocks of tpg tiles (fc2_deflate_launch_groups); 0: a block is a tile
     bool hung = false;                         // a wait timed out: the device is not touched again
     Slot slot[kSlots];
 };
@@ -211,23 +382,33 @@ static Wait wait_event(Gpu *g, Slot &s, std::string &err) {
     }
 }
 
-Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level, std::string &err) {
+Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level, uint32_t tile, uint32_t hist,
+              std::string &err) {
     if (!block || block > bgzf::kTileMax || !piece_blocks || piece_blocks > kMaxPieceBlocks || device < 0 || level < 1 ||
         level > 2) {
         err = "GPU BGZF: bad block size, piece size, device or level";
         return nullptr;
     }
+    if (tile >= block) tile = 0;                // (a block is one tile: today's launches, and no history to have)
+    if (tile && (hist > 32768u || tile + hist > 65536u || bgzf::tiles_per_group(block, tile) > bgzf::kTilesPerGroupMax)) {
+        err = "GPU BGZF: at most 16 tiles a block, a history of at most 32768 bytes, tile and history at most 65536 together";
+        return nullptr;
+    }
     Gpu *g = new Gpu();
     g->device = device;
     g->block = block;
-    g->stride = (FC2_DEFLATE_TILE_BOUND(block) + 15u) & ~15u;  // slots on 16-byte boundaries
-    g->max_tiles = piece_blocks;
+    g->tile = tile;
+    g->hist = tile ? hist : 0;
+    g->tpg = tile ? bgzf::tiles_per_group(block, tile) : 1;
+    g->stride = (FC2_DEFLATE_TILE_BOUND(tile ? tile : block) + 15u) & ~15u;  // slots on 16-byte boundaries
+    g->max_tiles = piece_blocks * g->tpg;
     g->max_piece = (size_t)block * piece_blocks;
-    g->out_cap = (size_t)piece_blocks * (bgzf::kOverhead + FC2_DEFLATE_TILE_BOUND(block));
+    g->out_cap = tile ? (size_t)piece_blocks * bgzf::kBlockMax      // (a block of tiles is framed only if it fits)
+                      : (size_t)piece_blocks * (bgzf::kOverhead + FC2_DEFLATE_TILE_BOUND(block));
     g->timeout_s = timeout_s > 0 ? timeout_s : kDefaultTimeout;
     g->level = level;
     const size_t slots = (size_t)g->max_tiles * g->stride, meta = ((size_t)g->max_tiles * 3 + 2) * sizeof(uint32_t),
-                 scratch = (size_t)fc2_deflate_scratch_bytes(g->max_piece, block);
+                 scratch = (size_t)fc2_deflate_scratch_bytes(g->max_piece, tile ? tile : block);
     bool ok = hip_ok(hipSetDevice(device), "hipSetDevice", err);
     for (int k = 0; k < kSlots && ok; ++k) {
         Slot &s = g->slot[k];
@@ -288,20 +469,29 @@ bool gpu_submit(Gpu *g, int k, const char *data, size_t n, std::string &err) {
     if (!hip_ok(hipSetDevice(g->device), "hipSetDevice", err)) return false;
     memcpy(s.h_src, data, n);
     s.n = n;
-    s.tiles = (uint32_t)((n + g->block - 1) / g->block);
+    s.tiles = g->tile ? (uint32_t)fc2_deflate_group_tiles(n, g->block, g->tile) : (uint32_t)((n + g->block - 1) / g->block);
     *s.h_total = 0;
     uint32_t *const d_len = s.d_meta, *const d_crc = s.d_meta + g->max_tiles, *const d_off = s.d_meta + 2 * (size_t)g->max_tiles,
                     *const d_total = d_off + g->max_tiles + 1;
     // (whatever was queued on the stream before a failure still runs: from the first call on the slot
     // counts as busy, and a failure drains the stream before the slot's buffers can be used again)
     s.busy = true;
+    auto compress = [&] {
+        return g->tile ? fc2_deflate_launch_groups(s.d_src, n, g->block, g->tile, g->hist, s.d_slots, g->stride, d_len, d_crc,
+                                                   s.d_scratch, s.stream, g->level)
+                       : fc2_deflate_launch_level(s.d_src, n, g->block, s.d_slots, g->stride, d_len, d_crc, s.d_scratch, s.stream,
+                                                  g->level);
+    };
+    auto frame = [&] {
+        return g->tile ? fc2_bgzf_frame_groups_launch(s.d_slots, g->stride, d_len, d_crc, s.tiles, n, g->block, g->tile, s.d_out,
+                                                      d_off, d_total, s.stream)
+                       : fc2_bgzf_frame_launch(s.d_slots, g->stride, d_len, d_crc, s.tiles, n, g->block, s.d_out, d_off, d_total,
+                                               s.stream);
+    };
     const bool ok =
         hip_ok(hipMemcpyAsync(s.d_src, s.h_src, n, hipMemcpyHostToDevice, s.stream), "upload", err) &&
-        (fc2_deflate_launch_level(s.d_src, n, g->block, s.d_slots, g->stride, d_len, d_crc, s.d_scratch, s.stream, g->level) ==
-             FC2_OK ||
-         ((err = "GPU BGZF: the compressor's launch failed"), false)) &&
-        (fc2_bgzf_frame_launch(s.d_slots, g->stride, d_len, d_crc, s.tiles, n, g->block, s.d_out, d_off, d_total, s.stream) ==
-             FC2_OK || ((err = "GPU BGZF: the framing launch failed"), false)) &&
+        (compress() == FC2_OK || ((err = "GPU BGZF: the compressor's launch failed"), false)) &&
+        (frame() == FC2_OK || ((err = "GPU BGZF: the framing launch failed"), false)) &&
         hip_ok(hipMemcpyAsync(s.h_total, d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream), "download", err) &&
         hip_ok(hipEventRecord(s.done, s.stream), "event", err);
     if (!ok) {
@@ -402,6 +592,13 @@ extern "C" uint64_t fc2_gpu_bgzf_bound(uint64_t n, uint32_t block) {
     return n + blocks * (kOverhead + 16);       // a block per `block` bytes: the stream at its worst and the 26 bytes around it
 }
 
+extern "C" uint64_t fc2_gpu_bgzf_tiles_bound(uint64_t n, uint32_t block, uint32_t tile) {
+    if (!block || block > kTileMax) return 0;
+    if (!tile || tile >= block) return fc2_gpu_bgzf_bound(n, block);
+    const uint64_t blocks = (n + block - 1) / block;
+    return n + blocks * (kOverhead + 16ull * tiles_per_group(block, tile));     // every tile's stream at its worst
+}
+
 extern "C" int fc2_gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, void *out,
                             uint64_t cap, uint64_t *out_n) {
     return fc2_gpu_bgzf_level(device, in, n, block, piece_blocks, 1, out, cap, out_n);
@@ -409,15 +606,22 @@ extern "C" int fc2_gpu_bgzf(int device, const void *in, uint64_t n, uint32_t blo
 
 extern "C" int fc2_gpu_bgzf_level(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, int level,
                                   void *out, uint64_t cap, uint64_t *out_n) {
+    return fc2_gpu_bgzf_tiles(device, in, n, block, piece_blocks, 0, 0, level, out, cap, out_n);
+}
+
+extern "C" int fc2_gpu_bgzf_tiles(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
+                                  uint32_t hist, int level, void *out, uint64_t cap, uint64_t *out_n) {
     using namespace fc2;
     if (!block || block > kTileMax || piece_blocks > bgz::kMaxPieceBlocks || device < 0 || !out || !out_n || (!in && n) ||
         level < 1 || level > 2)
         return fc2::fail(FC2_E_PARAM, "fc2_gpu_bgzf: bad arguments (block is 1..0xff00, piece_blocks at most 1024)");
+    if (tile && tile < block && (hist > 32768u || tile + hist > 65536u || tiles_per_group(block, tile) > kTilesPerGroupMax))
+        return fc2::fail(FC2_E_PARAM, "fc2_gpu_bgzf_tiles: at most 16 tiles a block, hist 0..32768, tile + hist <= 65536");
     *out_n = 0;
     if (!n) return FC2_OK;
     if (!piece_blocks) piece_blocks = bgz::kDefaultPieceBlocks;
     std::string err;
-    bgz::Gpu *g = bgz::gpu_open(device, block, piece_blocks, 0, level, err);
+    bgz::Gpu *g = bgz::gpu_open(device, block, piece_blocks, 0, level, tile, hist, err);
     if (!g) return fc2::fail(FC2_E_HIP, "fc2_gpu_bgzf: " + err);
     const char *src = static_cast<const char *>(in);
     uint8_t *o = static_cast<uint8_t *>(out);

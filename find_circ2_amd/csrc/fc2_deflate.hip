@@ -96,6 +96,27 @@
 //   LDS with a history: 22540 B + (tile + hist rounded up to 4) + 16, and at level 2 two bytes more per
 // position up to 32768.  Level 1: 8 KiB + 32 KiB 63516 B (two workgroups a CU), 32 KiB + 32 KiB 88092 B
 // (one).  Level 2: 8 KiB + 32 KiB 129052 B, 32 KiB + 32 KiB 153628 B (one a CU both).
+//
+// Groups (deflate_kernel<level, true, true>, fc2_deflate_launch_groups; tests/deflate_model_groups.py is the rule
+// in Python).  The launch's n bytes are cut into groups of `group` bytes, the last group holding the rest, and
+// every group is a DEFLATE stream of its own cut into tiles: a BGZF block compressed by several wavefronts.  A
+// whole group has tpg = ceil(group / tile) tiles, its last one holding the rest of the group; tiles are numbered
+// densely, tile g * tpg + k is the k-th of group g, and only the last group can have fewer than tpg.  The kernel
+// is the history's with three things derived from `group`: the tile's start g * group + k * tile, its history
+// h = min(hist, k * tile) -- never a byte before the group's first, none for a group's first tile -- and `last`,
+// true for the tile that ends its group (BFINAL = 1; every other tile in the non-final form above, with hist = 0
+// too: a group is one stream whatever hist is).  Pass 1, the link[] bounds argument with m = h + n <= tile + hist,
+// the Huffman and stored choice and the emission are the history's word for word.  One tile a group (tile >=
+// group) is <level, false> at tile = group byte for byte; with hist > 0 a group's slots are
+// fc2_deflate_launch_hist's over that group's bytes alone.
+//   Scratch.  A tile's tokens lie at scratch + 4 * (its first byte's offset in src), at most one per byte of
+// the tile: tiles cover disjoint bytes, so 4 * n_bytes suffice, which fc2_deflate_scratch_bytes(n_bytes, tile)
+// is at least.  Slots, out_len and crc have fc2_deflate_group_tiles(n_bytes, group, tile) entries.
+//   Instantiations.  <.., false> and <.., true> got one more unread kernel argument (`group`); their
+// instructions are those from before the groups, compared in the compiler's output.  Resource report for
+// gfx950 as above:   <1, true, true> 47, 74, 0    <2, true, true> 47, 78, 0
+//   LDS by the formula above at tile 0x3fc0 with 32 KiB of history (region 49088 B): level 1 71644 B, two
+// workgroups a CU; level 2 137180 B, one.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -333,12 +354,15 @@ __device__ __forceinline__ void put(Lds &L, Out &o, uint32_t v, uint32_t nb) {
 }
 
 // kHist: the launch is one DEFLATE stream, and a tile has the `hist` bytes before it in front of it in LDS
-// (the header's "History"); without it `hist` is not looked at.
-template <int kLevel, bool kHist>
+// (the header's "History"); without it `hist` is not looked at.  kGroups (with kHist): the launch is cut into
+// groups of `group` bytes, each a stream of its own whose tiles see only their group (the header's "Groups");
+// without it `group` is not looked at.
+template <int kLevel, bool kHist, bool kGroups = false>
 __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__ src, uint64_t n_bytes, uint32_t tile,
                                                      uint8_t *__restrict__ dst, uint32_t stride,
                                                      uint32_t *__restrict__ out_len, uint32_t *__restrict__ crc,
-                                                     uint32_t *__restrict__ scratch, uint32_t hist) {
+                                                     uint32_t *__restrict__ scratch, uint32_t hist, uint32_t group) {
+    static_assert(kHist || !kGroups, "groups are built on the history's kernel");
     extern __shared__ __align__(16) uint8_t smem[];
     Lds &L = *reinterpret_cast<Lds *>(smem);
     uint32_t *T = L.tile;
@@ -349,14 +373,22 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     }
     const uint32_t blk = blockIdx.x;
     const int lane = (int)threadIdx.x;
-    const uint64_t start = (uint64_t)blk * tile;
-    if (start >= n_bytes) return;
-    const uint32_t n = (uint32_t)(n_bytes - start < (uint64_t)tile ? n_bytes - start : (uint64_t)tile);   // 1..65536
+    uint64_t start = (uint64_t)blk * tile;
+    uint64_t from = 0, upto = n_bytes;          // the stream the tile belongs to: the launch, or its group
+    if constexpr (kGroups) {
+        const uint32_t tpg = (group - 1u) / tile + 1u;      // tiles of a whole group: tile g * tpg + k is group g's k-th
+        const uint32_t g = blk / tpg, k = blk - g * tpg;
+        from = (uint64_t)g * group;
+        start = from + (uint64_t)k * tile;
+        if (from + group < upto) upto = from + group;
+    }
+    if (start >= upto) return;
+    const uint32_t n = (uint32_t)(upto - start < (uint64_t)tile ? upto - start : (uint64_t)tile);   // 1..65536
     // the region in LDS: h bytes of history, then the tile; m bytes, positions counted from the history's first
     uint32_t h = 0;
-    if constexpr (kHist) h = (uint32_t)(start < (uint64_t)hist ? start : (uint64_t)hist);
+    if constexpr (kHist) h = (uint32_t)(start - from < (uint64_t)hist ? start - from : (uint64_t)hist);
     const uint32_t m = h + n;                   // 1..65536
-    const bool last = !kHist || start + n >= n_bytes;   // written as a stream of its own: BFINAL, nothing after it
+    const bool last = !kHist || start + n >= upto;      // written as a stream of its own: BFINAL, nothing after it
     const uint8_t *in = src + start - h;
     uint8_t *slot = dst + (uint64_t)blk * stride;
     uint32_t *tok = scratch + start;           // n tokens at most
@@ -729,16 +761,22 @@ size_t lds_bytes(uint32_t tile, int level) {     // (with a history: of tile + h
     return offsetof(Lds, tile) + held + 16u + (level == 2 ? 2u * (held < kLinks ? held : kLinks) : 0u);
 }
 
-template <int kLevel, bool kHist>
+// tiles of a launch over groups: whole groups have (group - 1) / tile + 1 each, the last group those of its bytes
+uint64_t group_tiles(uint64_t n_bytes, uint32_t group, uint32_t tile) {
+    const uint64_t tpg = (group - 1u) / tile + 1u, rest = n_bytes % group;
+    return n_bytes / group * tpg + (rest + tile - 1) / tile;
+}
+
+template <int kLevel, bool kHist, bool kGroups = false>
 int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, uint8_t *dst, uint32_t stride, uint32_t *out_len,
-           uint32_t *crc, void *scratch, void *stream) {
+           uint32_t *crc, void *scratch, void *stream, uint32_t group = 0) {
     if (!tile || tile > kTileMax) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: tile must be 1..65536");
     if (stride < FC2_DEFLATE_TILE_BOUND(tile))
         return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: stride below FC2_DEFLATE_TILE_BOUND(tile)");
     if (!n_bytes) return FC2_OK;
     if (!src || !dst || !out_len || !crc || !scratch) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: null argument");
     if (((uintptr_t)scratch & 3u) != 0) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: scratch must be 4-byte aligned");
-    const uint64_t tiles = (n_bytes + tile - 1) / tile;
+    const uint64_t tiles = kGroups ? group_tiles(n_bytes, group, tile) : (n_bytes + tile - 1) / tile;
     if (tiles > 0x7FFFFFFFull) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: too many tiles for one launch");
     // the kernel's LDS (over the 64 KiB a kernel gets unasked, for the larger tiles): once per device and instantiation
     static std::atomic<uint64_t> reserved{0};
@@ -746,14 +784,14 @@ int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, u
     if (hipGetDevice(&dev) != hipSuccess) return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: no current device");
     const uint64_t bit = 1ull << (dev & 63);
     if (!(reserved.load() & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel<kLevel, kHist>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel<kLevel, kHist, kGroups>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kTileMax, kLevel)) != hipSuccess)
             return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: cannot reserve the kernel's LDS");
         reserved |= bit;
     }
-    hipLaunchKernelGGL((deflate_kernel<kLevel, kHist>), dim3((uint32_t)tiles), dim3(64), lds_bytes(tile + hist, kLevel),
+    hipLaunchKernelGGL((deflate_kernel<kLevel, kHist, kGroups>), dim3((uint32_t)tiles), dim3(64), lds_bytes(tile + hist, kLevel),
                        (hipStream_t)stream, src, n_bytes, tile, dst, stride, out_len, crc, static_cast<uint32_t *>(scratch),
-                       hist);
+                       hist, group);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_deflate_launch: ") + hipGetErrorString(e));
 }
@@ -787,4 +825,20 @@ extern "C" int fc2_deflate_launch_hist(const uint8_t *src, uint64_t n_bytes, uin
     if (!hist) return fc2_deflate_launch_level(src, n_bytes, tile, dst, stride, out_len, crc, scratch, stream, level);
     if (level == 1) return launch<1, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream);
     return launch<2, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream);
+}
+
+extern "C" uint64_t fc2_deflate_group_tiles(uint64_t n_bytes, uint32_t group, uint32_t tile) {
+    if (!tile || tile > kTileMax || !group) return 0;
+    return group_tiles(n_bytes, group, tile);
+}
+
+extern "C" int fc2_deflate_launch_groups(const uint8_t *src, uint64_t n_bytes, uint32_t group, uint32_t tile, uint32_t hist,
+                                         uint8_t *dst, uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch,
+                                         void *stream, int level) {
+    if (level != 1 && level != 2) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_groups: level is 1 or 2");
+    if (!group || !tile || tile > kTileMax || hist > kMaxDist || tile + hist > kTileMax)
+        return fc2::fail(FC2_E_PARAM,
+                         "fc2_deflate_launch_groups: group must be >= 1, tile 1..65536, hist 0..32768, tile + hist <= 65536");
+    if (level == 1) return launch<1, true, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, group);
+    return launch<2, true, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, group);
 }

@@ -642,6 +642,7 @@ struct fc2_ingest {
     std::string bam_err;
     uint64_t bam_gpu_pieces = 0, bam_cpu_pieces = 0;    // fc2_ingest_bam_out_counts, once the writer is closed
     int bam_level = 1;                          // fc2_ingest_set_bam_out_device_level
+    uint32_t bam_tile = 0, bam_hist = 0;        // fc2_ingest_set_bam_out_device_tiles
     // grouping state
     bool started = false;
     Mate current, other;
@@ -2401,9 +2402,25 @@ extern "C" int fc2_ingest_set_bam_out_device(fc2_ingest *h, int mode, int device
     if (mode < 0 || mode > 2 || block > 0xff00 || piece_blocks > 1024 || timeout_s < 0 || (mode == 1 && device < 0))
         return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: mode is 0, 1 or 2, block at most 0xff00, "
                                       "piece_blocks at most 1024");
+    const uint32_t cut = block ? block : 0xff00u, tile = h->bam_tile;     // (fc2_ingest_set_bam_out_device_tiles)
+    if (mode && tile && tile < cut && ((cut - 1) / tile + 1 > 16 || tile + h->bam_hist > 65536))
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: at most 16 tiles a block, and tile and history at most "
+                                      "65536 bytes together");
     std::string err;
-    if (!fc2::bam::set_device(h->bam_out, mode, device, block, piece_blocks, timeout_s, h->bam_level, err))
+    if (!fc2::bam::set_device(h->bam_out, mode, device, block, piece_blocks, timeout_s, h->bam_level, h->bam_tile,
+                              h->bam_hist, err))
         return fc2::fail(mode == 1 ? FC2_E_HIP : FC2_E_PARAM, "fc2_ingest_set_bam_out_device: " + err);
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_set_bam_out_device_tiles(fc2_ingest *h, uint32_t tile, uint32_t hist) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_tiles: null argument");
+    if (!h->bam_out || h->n_records || fc2::bam::device_set(h->bam_out))
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_tiles: call after fc2_ingest_set_bam_out, before "
+                                      "fc2_ingest_set_bam_out_device and before reading");
+    if (hist > 32768) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_tiles: hist is 0..32768");
+    h->bam_tile = tile;
+    h->bam_hist = hist;
     return FC2_OK;
 }
 

@@ -53,7 +53,8 @@ class NativeIngest:
         """-B/--bam: anchor alignments to ``path`` (include/fc2_ingest.h).  bam_device: None, or the
         arguments of fc2_ingest_set_bam_out_device as a dict -- mode (1: the records compressed on GPU
         ``device``; 2: by the host model of it, a test setting), device, block, piece_blocks, timeout_s
-        (each 0 or absent: the default), level (the GPU compressor's, 1 or 2; absent: 1)."""
+        (each 0 or absent: the default), level (the GPU compressor's, 1 or 2; absent: 1), tile and hist
+        (fc2_ingest_set_bam_out_device_tiles; absent or 0: a block is one tile)."""
         N.check(N.lib().fc2_ingest_set_bam_out(self.h, path.encode()))
         if bam_device:
             set_bam_out_device(self.h, bam_device)
@@ -138,6 +139,8 @@ def set_bam_out_device(h, bam_device) -> None:
     d = dict(bam_device)
     if int(d.get("level", 1)) != 1:
         N.check(N.lib().fc2_ingest_set_bam_out_device_level(h, int(d["level"])))
+    if int(d.get("tile", 0)) or int(d.get("hist", 0)):
+        N.check(N.lib().fc2_ingest_set_bam_out_device_tiles(h, int(d.get("tile", 0)), int(d.get("hist", 0))))
     N.check(N.lib().fc2_ingest_set_bam_out_device(h, int(d.get("mode", 1)), int(d.get("device", 0)), int(d.get("block", 0)),
                                                   int(d.get("piece_blocks", 0)), float(d.get("timeout_s", 0.0))))
 

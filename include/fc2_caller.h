@@ -166,6 +166,24 @@ int fc2_deflate_launch_level(const uint8_t *src, uint64_t n_bytes, uint32_t tile
 int fc2_deflate_launch_hist(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, uint8_t *dst,
                             uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch, void *stream, int level);
 uint64_t fc2_deflate_scratch_bytes(uint64_t n_bytes, uint32_t tile);
+/* The compressor over groups: src[0, n_bytes) is cut into groups of `group` bytes (the last holds the rest), every
+ * group into tiles of `tile` bytes (a group's last tile holds its rest).  Tiles are numbered densely: tile
+ * g * tpg + k is the k-th of group g, tpg = ceil(group / tile), and only the last group can have fewer than tpg;
+ * fc2_deflate_group_tiles gives their number, the entries of out_len and crc and the slots at dst + i * stride.
+ * Tile k of a group may refer to the min(hist, k * tile) input bytes before it, never to a byte before its group's
+ * first.  Every group is one raw DEFLATE stream, whatever hist is: its last tile is written with BFINAL = 1, every
+ * other tile in fc2_deflate_launch_hist's non-final form, so a group's streams back to back, in order, inflate to
+ * the group's bytes.  crc[i] is the CRC-32 of tile i's own bytes; out_len[i] <= FC2_DEFLATE_TILE_BOUND(tile);
+ * nothing outside [slot, slot + out_len) is written.  With hist > 0 a group's slots are fc2_deflate_launch_hist's
+ * over that group's bytes alone; with one tile a group (tile >= group) the launch is fc2_deflate_launch_level at
+ * tile = group byte for byte.  group >= 1, tile 1..65536, hist 0..32768, tile + hist <= 65536, level 1 or 2:
+ * anything else is FC2_E_PARAM before the device is touched.  scratch: fc2_deflate_scratch_bytes(n_bytes, tile)
+ * bytes of device memory (a tile's tokens lie at its input's offset, so 4 * n_bytes are what is used). */
+int fc2_deflate_launch_groups(const uint8_t *src, uint64_t n_bytes, uint32_t group, uint32_t tile, uint32_t hist,
+                              uint8_t *dst, uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch,
+                              void *stream, int level);
+/* tiles of fc2_deflate_launch_groups over n_bytes (0 for group 0 or a tile outside 1..65536) */
+uint64_t fc2_deflate_group_tiles(uint64_t n_bytes, uint32_t group, uint32_t tile);
 /* one buffer through the host path of spliced_reads.fastq.gz's device mode, for tests and other hosts: gzip
  * members (one per tile) of in[0, n) into out (cap bytes); FC2_E_RANGE if they do not fit. */
 int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, void *out, uint64_t cap, uint64_t *out_n);
@@ -203,7 +221,30 @@ int fc2_gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_
 /* fc2_gpu_bgzf with the blocks compressed at `level` (1 or 2, fc2_deflate_launch_level; else FC2_E_PARAM) */
 int fc2_gpu_bgzf_level(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, int level,
                        void *out, uint64_t cap, uint64_t *out_n);
+/* fc2_gpu_bgzf_level with every block cut into tiles of `tile` bytes that have up to `hist` bytes of their block
+ * before them as history (fc2_deflate_launch_groups, fc2_bgzf_frame_groups_launch): at most 16 tiles a block, hist
+ * 0..32768, tile + hist <= 65536, else FC2_E_PARAM.  tile = 0 or tile >= block: fc2_gpu_bgzf_level's bytes. */
+int fc2_gpu_bgzf_tiles(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
+                       uint32_t hist, int level, void *out, uint64_t cap, uint64_t *out_n);
+/* the bytes fc2_gpu_bgzf_tiles needs at most: fc2_gpu_bgzf_bound's with every tile's stream at its worst */
+uint64_t fc2_gpu_bgzf_tiles_bound(uint64_t n, uint32_t block, uint32_t tile);
 uint64_t fc2_gpu_bgzf_bound(uint64_t n, uint32_t block);
+/* fc2_bgzf_frame_launch for blocks of several tiles, the slots fc2_deflate_launch_groups filled (n_tiles =
+ * fc2_deflate_group_tiles(n_bytes, group, tile)): block g -- the 18 header bytes, the streams of group g's tiles
+ * back to back in order, the group's CRC-32 combined from the tiles' CRCs and lengths (the input is not read),
+ * ISIZE = the group's input bytes -- at out + off[g]; off has one entry per group and the end, *total =
+ * off[n_groups].  out holds min(65536, 26 + tpg * FC2_DEFLATE_TILE_BOUND(tile)) bytes a group.  A tile whose
+ * out_len is 0xFFFFFFFF, 0 or above the bound, or a block of more than 65536 bytes, makes the piece unwritten:
+ * *total = 0, every offset 0, no byte of out touched.  FC2_E_PARAM (nothing launched) unless group is 1..0xff00,
+ * tile 1..65536 with at most 16 tiles a group, there are at most 65535 groups and n_tiles is their tiles' number.
+ * One tile a group: fc2_bgzf_frame_launch's bytes.  All pointers are device memory; two kernels on `stream`. */
+int fc2_bgzf_frame_groups_launch(const uint8_t *slots, uint32_t stride, const uint32_t *out_len, const uint32_t *crc,
+                                 uint32_t n_tiles, uint64_t n_bytes, uint32_t group, uint32_t tile, uint8_t *out,
+                                 uint32_t *off, uint32_t *total, void *stream);
+/* the same rule on host memory (slots at any alignment); *total = 0 also when the arguments are refused */
+int fc2_bgzf_frame_groups_host(const uint8_t *slots, uint32_t stride, const uint32_t *out_len, const uint32_t *crc,
+                               uint32_t n_tiles, uint64_t n_bytes, uint32_t group, uint32_t tile, uint8_t *out,
+                               uint32_t *off, uint32_t *total);
 
 /* The BED rows (no header) of 0 = circ_splice_sites.bed, 1 = lin_splice_sites.bed
  * (call once, at the end).  Once the input was read to its end and every chunk submitted, the first

@@ -100,6 +100,16 @@ int fc2_ingest_set_bam_out_device(fc2_ingest *h, int mode, int device, uint32_t 
  * device mode set afterwards with fc2_ingest_set_bam_out_device; mode 2 ignores it.  FC2_E_PARAM for another
  * level or a call after reading has begun.  The command line passes FC2_GPU_BAM_LEVEL here. */
 int fc2_ingest_set_bam_out_device_level(fc2_ingest *h, int level);
+/* Tiles inside a block, for the device mode set afterwards with fc2_ingest_set_bam_out_device: every block of the
+ * record bytes is cut into tiles of `tile` bytes, each compressed by a wavefront of its own with the min(hist,
+ * its offset in the block) bytes of its block before it as history, and the block's streams, combined CRC-32 and
+ * ISIZE are put together on the device (fc2_deflate_launch_groups, fc2_bgzf_frame_groups_launch,
+ * include/fc2_caller.h).  tile = 0 (the default) or tile >= block: a block is one tile, and hist is not used.
+ * Mode 2 flushes zlib at the tiles' ends and frames with fc2_bgzf_frame_groups_host.  FC2_E_PARAM for hist over
+ * 32768 and for a call after fc2_ingest_set_bam_out_device or after reading has begun; more than 16 tiles a block
+ * and tile + hist over 65536 are refused by fc2_ingest_set_bam_out_device itself (FC2_E_PARAM), which then leaves
+ * the CPU writer in place.  The command line passes FC2_GPU_BAM_TILE and FC2_GPU_BAM_HISTORY here. */
+int fc2_ingest_set_bam_out_device_tiles(fc2_ingest *h, uint32_t tile, uint32_t hist);
 /* pieces the device (mode 2: its host model) compressed, and pieces of the device mode zlib compressed, so
  * far; final after fc2_ingest_close_bam_out (0, 0 without the device mode) */
 int fc2_ingest_bam_out_counts(const fc2_ingest *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces);
