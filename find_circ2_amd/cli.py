@@ -303,20 +303,36 @@ def _gpu_group():
     return 1 if os.environ.get("FC2_GPU_GROUP") == "1" else 0
 
 
+def _search_env(prefix):
+    """(depth, nice) of level 2's search effort from ``prefix``_DEPTH and ``prefix``_NICE (DESIGN.md §5 "Search
+    effort at level 2"), or None with both unset or empty; one alone leaves the other at level 2's own (8, 32).
+    The library judges the values, and that level 2 is set."""
+    depth, nice = os.environ.get(prefix + "_DEPTH"), os.environ.get(prefix + "_NICE")
+    if not depth and not nice:
+        return None
+    return (int(depth) if depth else 8, int(nice) if nice else 32)
+
+
+def _search_note(tag, search) -> str:
+    return ", %s_gpu_depth=%d, %s_gpu_nice=%d" % (tag, search[0], tag, search[1]) if search else ""
+
+
 def _gzip_device(options):
     """spliced_reads.fastq.gz compressed on the GPU: only with FC2_GPU_GZIP=1, on the first of
     the run's devices, in tiles of FC2_GPU_GZIP_TILE bytes (32768), waiting at most
     FC2_GPU_GZIP_TIMEOUT_S seconds (60) for the device, at the compressor's level 2 with FC2_GPU_GZIP_LEVEL=2
     (unset or anything else: level 1), every tile referring to the FC2_GPU_GZIP_HISTORY bytes of its piece
-    before it (unset, empty or 0: none; DESIGN.md §5 "History across the tiles").  Anything but 1: {}, the
-    worker threads compress."""
+    before it (unset, empty or 0: none; DESIGN.md §5 "History across the tiles"), level 2 searching with
+    FC2_GPU_GZIP_DEPTH candidates (1..128) up to a length of FC2_GPU_GZIP_NICE (4..258; both unset or empty: its
+    own 8 and 32; without FC2_GPU_GZIP_LEVEL=2 or out of range the library refuses them and the run ends).
+    Anything but 1: {}, the worker threads compress and none of these is read."""
     if os.environ.get("FC2_GPU_GZIP") != "1":
         return {}
     from .ctxpipe import device_index
     return dict(gzip_device=device_index(options.device), gzip_tile=int(os.environ.get("FC2_GPU_GZIP_TILE") or 0),
                 gzip_timeout_s=float(os.environ.get("FC2_GPU_GZIP_TIMEOUT_S") or 0),
                 gzip_level=2 if os.environ.get("FC2_GPU_GZIP_LEVEL") == "2" else 1,
-                gzip_history=int(os.environ.get("FC2_GPU_GZIP_HISTORY") or 0))
+                gzip_history=int(os.environ.get("FC2_GPU_GZIP_HISTORY") or 0), gzip_search=_search_env("FC2_GPU_GZIP"))
 
 
 def _bam_device(options):
@@ -325,14 +341,18 @@ def _bam_device(options):
     for it, at the compressor's level 2 with FC2_GPU_BAM_LEVEL=2 (unset or anything else: level 1), every block
     cut into tiles of FC2_GPU_BAM_TILE bytes (unset, empty or 0: the block is one tile) that see the
     FC2_GPU_BAM_HISTORY bytes (0..32768; unset, empty or 0: none) of their block before them (DESIGN.md §5
-    "Tiles inside a BGZF block").  Unset, 0 or anything else: None, zlib compresses on the reading thread, and
-    neither of the two is read."""
+    "Tiles inside a BGZF block"), level 2 searching with FC2_GPU_BAM_DEPTH candidates (1..128) up to a length of
+    FC2_GPU_BAM_NICE (4..258; both unset or empty: its own 8 and 32; without FC2_GPU_BAM_LEVEL=2 or out of range
+    the library refuses them and the run ends).  Unset, 0 or anything else: None, zlib compresses on the reading
+    thread, and none of these is read."""
     if os.environ.get("FC2_GPU_BAM") != "1":
         return None
     from .ctxpipe import device_index
+    search = _search_env("FC2_GPU_BAM")
     return dict(mode=1, device=device_index(options.device), timeout_s=float(os.environ.get("FC2_GPU_BAM_TIMEOUT_S") or 0),
                 level=2 if os.environ.get("FC2_GPU_BAM_LEVEL") == "2" else 1,
-                tile=int(os.environ.get("FC2_GPU_BAM_TILE") or 0), hist=int(os.environ.get("FC2_GPU_BAM_HISTORY") or 0))
+                tile=int(os.environ.get("FC2_GPU_BAM_TILE") or 0), hist=int(os.environ.get("FC2_GPU_BAM_HISTORY") or 0),
+                **(dict(depth=search[0], nice=search[1]) if search else {}))
 
 
 def _bam_tiles_note(bam_device) -> str:
@@ -428,7 +448,10 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                 startup.update(zip(("bam_gpu_pieces", "bam_cpu_pieces"), nc.bam_out_pieces))
             levels = (", gzip_gpu_level=2" if nc.gzip_device is not None and nc.gzip_level == 2 else "") + \
                 (", gzip_gpu_history=%d" % nc.gzip_history if nc.gzip_device is not None and nc.gzip_history > 0 else "") + \
-                (", bam_gpu_level=2" if nc.bam_device and nc.bam_device.get("level") == 2 else "") + _bam_tiles_note(nc.bam_device)
+                (", bam_gpu_level=2" if nc.bam_device and nc.bam_device.get("level") == 2 else "") + _bam_tiles_note(nc.bam_device) + \
+                _search_note("gzip", nc.gzip_search if nc.gzip_device is not None else None) + \
+                _search_note("bam", (nc.bam_device["depth"], nc.bam_device["nice"])
+                             if nc.bam_device and nc.bam_device.get("depth") is not None else None)
             logger.info("process phases: " + ", ".join("%s=%.3f" % kv for kv in startup.items()) + levels +
                         ", process_age_s=%.3f, numpy_loaded=%d, torch_loaded=%d"
                         % (process_age(), "numpy" in sys.modules, "torch" in sys.modules))

@@ -349,6 +349,7 @@ struct Gpu {
     double timeout_s = kDefaultTimeout;
     int level = 1;                             // fc2_deflate_launch_level's
     uint32_t tile = 0, hist = 0, tpg = 1;      // tile > 0: blocks of tpg tiles (fc2_deflate_launch_groups); 0: a block is a tile
+    uint32_t depth = 0, nice = 0;              // depth > 0: fc2_deflate_launch_deep with these (level 2 only)
     bool hung = false;                         // a wait timed out: the device is not touched again
     Slot slot[kSlots];
 };
@@ -384,9 +385,17 @@ static Wait wait_event(Gpu *g, Slot &s, std::string &err) {
 
 Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level, uint32_t tile, uint32_t hist,
               std::string &err) {
+    // (level_with_search: level 2's search effort rides in the level's upper bits)
+    const uint32_t depth = ((uint32_t)level >> 8) & 0xFFu, nice = ((uint32_t)level >> 16) & 0x1FFu;
+    if (level > 0 && (depth || nice)) level &= 0xFF;
     if (!block || block > bgzf::kTileMax || !piece_blocks || piece_blocks > kMaxPieceBlocks || device < 0 || level < 1 ||
         level > 2) {
         err = "GPU BGZF: bad block size, piece size, device or level";
+        return nullptr;
+    }
+    if ((depth || nice) && (level != 2 || depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX ||
+                            nice < FC2_DEFLATE_NICE_MIN || nice > FC2_DEFLATE_NICE_MAX)) {
+        err = "GPU BGZF: the search effort needs level 2, depth 1..128 and nice 4..258";
         return nullptr;
     }
     if (tile >= block) tile = 0;                // (a block is one tile: today's launches, and no history to have)
@@ -407,6 +416,8 @@ Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_
                       : (size_t)piece_blocks * (bgzf::kOverhead + FC2_DEFLATE_TILE_BOUND(block));
     g->timeout_s = timeout_s > 0 ? timeout_s : kDefaultTimeout;
     g->level = level;
+    g->depth = depth;
+    g->nice = nice;
     const size_t slots = (size_t)g->max_tiles * g->stride, meta = ((size_t)g->max_tiles * 3 + 2) * sizeof(uint32_t),
                  scratch = (size_t)fc2_deflate_scratch_bytes(g->max_piece, tile ? tile : block);
     bool ok = hip_ok(hipSetDevice(device), "hipSetDevice", err);
@@ -477,6 +488,9 @@ bool gpu_submit(Gpu *g, int k, const char *data, size_t n, std::string &err) {
     // counts as busy, and a failure drains the stream before the slot's buffers can be used again)
     s.busy = true;
     auto compress = [&] {
+        if (g->depth)                           // (group = block: one tile a block is fc2_deflate_launch_level's shape)
+            return fc2_deflate_launch_deep(s.d_src, n, g->tile ? g->block : 0, g->tile ? g->tile : g->block, g->hist, s.d_slots,
+                                           g->stride, d_len, d_crc, s.d_scratch, s.stream, g->depth, g->nice);
         return g->tile ? fc2_deflate_launch_groups(s.d_src, n, g->block, g->tile, g->hist, s.d_slots, g->stride, d_len, d_crc,
                                                    s.d_scratch, s.stream, g->level)
                        : fc2_deflate_launch_level(s.d_src, n, g->block, s.d_slots, g->stride, d_len, d_crc, s.d_scratch, s.stream,
@@ -609,8 +623,27 @@ extern "C" int fc2_gpu_bgzf_level(int device, const void *in, uint64_t n, uint32
     return fc2_gpu_bgzf_tiles(device, in, n, block, piece_blocks, 0, 0, level, out, cap, out_n);
 }
 
+namespace {
+int gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile, uint32_t hist, int level,
+             uint32_t depth, uint32_t nice, void *out, uint64_t cap, uint64_t *out_n);
+}  // namespace
+
 extern "C" int fc2_gpu_bgzf_tiles(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
                                   uint32_t hist, int level, void *out, uint64_t cap, uint64_t *out_n) {
+    return gpu_bgzf(device, in, n, block, piece_blocks, tile, hist, level, 0, 0, out, cap, out_n);
+}
+
+extern "C" int fc2_gpu_bgzf_deep(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
+                                 uint32_t hist, uint32_t depth, uint32_t nice, void *out, uint64_t cap, uint64_t *out_n) {
+    if (depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX || nice < FC2_DEFLATE_NICE_MIN ||
+        nice > FC2_DEFLATE_NICE_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_gpu_bgzf_deep: depth is 1..128, nice 4..258");
+    return gpu_bgzf(device, in, n, block, piece_blocks, tile, hist, 2, depth, nice, out, cap, out_n);
+}
+
+namespace {
+int gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile, uint32_t hist, int level,
+             uint32_t depth, uint32_t nice, void *out, uint64_t cap, uint64_t *out_n) {
     using namespace fc2;
     if (!block || block > kTileMax || piece_blocks > bgz::kMaxPieceBlocks || device < 0 || !out || !out_n || (!in && n) ||
         level < 1 || level > 2)
@@ -621,7 +654,7 @@ extern "C" int fc2_gpu_bgzf_tiles(int device, const void *in, uint64_t n, uint32
     if (!n) return FC2_OK;
     if (!piece_blocks) piece_blocks = bgz::kDefaultPieceBlocks;
     std::string err;
-    bgz::Gpu *g = bgz::gpu_open(device, block, piece_blocks, 0, level, tile, hist, err);
+    bgz::Gpu *g = bgz::gpu_open(device, block, piece_blocks, 0, depth ? bgz::level_with_search(depth, nice) : level, tile, hist, err);
     if (!g) return fc2::fail(FC2_E_HIP, "fc2_gpu_bgzf: " + err);
     const char *src = static_cast<const char *>(in);
     uint8_t *o = static_cast<uint8_t *>(out);
@@ -661,3 +694,4 @@ extern "C" int fc2_gpu_bgzf_tiles(int device, const void *in, uint64_t n, uint32
     if (rc == FC2_OK) *out_n = at;
     return rc;
 }
+}  // namespace

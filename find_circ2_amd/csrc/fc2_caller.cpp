@@ -890,6 +890,7 @@ struct fc2_caller {
     double gz_timeout_s = 0;
     int gz_level = 1;                           // fc2_caller_set_reads_gz_device_level
     uint32_t gz_hist = 0;                       // fc2_caller_set_reads_gz_device_history
+    uint32_t gz_depth = 0, gz_nice = 0;         // fc2_caller_set_reads_gz_device_search (0, 0: the level's own)
     uint64_t n_chunks = 0;                      // chunks formed (next side)
 };
 
@@ -2707,7 +2708,10 @@ extern "C" int fc2_caller_set_reads_gz_device(fc2_caller *h, int device) {
     std::string err;
     if ((h->gz_tile ? h->gz_tile : fc2::dgz::kDefaultTile) + h->gz_hist > 65536)
         return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: tile + history over 65536 (the CPU writer stays)");
-    if (!h->reads_gz.set_device(device, h->gz_tile, h->gz_timeout_s, h->gz_level, h->gz_hist, err)) return fc2::fail(FC2_E_HIP, "fc2_caller_set_reads_gz_device: " + err);
+    if (h->gz_depth && h->gz_level != 2)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: the search effort needs level 2 (the CPU writer stays)");
+    if (!h->reads_gz.set_device(device, h->gz_tile, h->gz_timeout_s, h->gz_level, h->gz_hist, err, h->gz_depth, h->gz_nice))
+        return fc2::fail(FC2_E_HIP, "fc2_caller_set_reads_gz_device: " + err);
     return FC2_OK;
 }
 
@@ -2727,6 +2731,19 @@ extern "C" int fc2_caller_set_reads_gz_device_level(fc2_caller *h, int level) {
     if (h->reads_gz.device_mode())
         return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_level: call before fc2_caller_set_reads_gz_device");
     h->gz_level = level;
+    return FC2_OK;
+}
+
+extern "C" int fc2_caller_set_reads_gz_device_search(fc2_caller *h, uint32_t depth, uint32_t nice) {
+    if (!h || depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX || nice < FC2_DEFLATE_NICE_MIN ||
+        nice > FC2_DEFLATE_NICE_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_search: null handle, or not depth 1..128 and nice 4..258");
+    if (h->reads_gz.device_mode())
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_search: call before fc2_caller_set_reads_gz_device");
+    if (h->gz_level != 2)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_search: set level 2 first (fc2_caller_set_reads_gz_device_level)");
+    h->gz_depth = depth;
+    h->gz_nice = nice;
     return FC2_OK;
 }
 

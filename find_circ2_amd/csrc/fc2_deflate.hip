@@ -117,6 +117,32 @@
 // gfx950 as above:   <1, true, true> 47, 74, 0    <2, true, true> 47, 78, 0
 //   LDS by the formula above at tile 0x3fc0 with 32 KiB of history (region 49088 B): level 1 71644 B, two
 // workgroups a CU; level 2 137180 B, one.
+//
+// Search effort (deflate_kernel<2, .., .., true>, fc2_deflate_launch_deep; tests/deflate_model_deep.py is the rule in
+// Python).  Level 2's pass 1 with its two limits as kernel arguments, the same for every lane of every wavefront:
+// `depth`, the candidates a position walks at most (1..128; level 2 itself: kDepth = 8), and `nice`, the kept length
+// that ends the walk (4..258; level 2 itself: kNice = 32); one argument carries both, depth | nice << 16.  Nothing
+// else differs: links written with the head read before the step's positions enter, the walk's ends (no candidate,
+// over 32768 back, c + 32768 < base + 64), the first found among equal lengths, the cost rule, the lazy step and
+// everything after pass 1 are level 2's, in all three shapes (independent tiles, history, groups).  At depth 8 and
+// nice 32 the streams are level 2's byte for byte.  nice >= 258 leaves only the cap (min(258, m - p)) to end a walk
+// early; nice = 4 ends it at the first candidate whose four bytes fit.
+//   Bounds (link[]) for a walk of up to 128 candidates.  The argument above never used the 8.  It rests on two
+// things.  The falling candidate: the first c is a head of an earlier step, c < p, and every further one is c - back
+// with 1 <= back <= c checked before the subtraction, so c falls strictly, stays >= 0 and below p, and a walk ends
+// after at most p steps whatever `depth` says -- the host refuses depth > 128, but no load depends on that.  The
+// stale-slot stop: every c walked entered itself and wrote link[c & 32767]; that slot holds c's entry and not
+// c + 32768's, because the walk ends before reading it where c + 32768 < base + 64 (the only positions entered after
+// c that share its slot are >= c + 32768, and positions >= base + 64 have not been entered).  This is per candidate,
+// not per walk, so it holds at the 9th and the 128th as at the 1st.  Loads of link[] are at c & 32767 < min(region
+// rounded up to 4, 32768) since c < m; tile bytes are read up to c + 258 + 3 < m + 16.  The deep instantiations add
+// no LDS (link[] is level 2's), no store to global memory, no scratch byte, and FC2_DEFLATE_TILE_BOUND is unchanged.
+//   Divergence.  A wavefront's step takes as long as its lane with the longest walk: up to `depth` rounds of one
+// LDS read of link[], two of the tile (load32u) and, where the four bytes fit, the extension.  Lanes whose walk has
+// ended idle under the exec mask.  No cheaper schedule is tried here: the bytes are the model's.
+//   Instantiations.  The six kernels above got one more unread kernel argument (`search`); their instructions are
+// those of before, compared in the compiler's output (one symbol's name differs).  Resource report for gfx950
+// as above:   <2, false, false, true> 48, 76, 0    <2, true, false, true> 47, 82, 0    <2, true, true, true> 47, 82, 0
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -357,12 +383,16 @@ __device__ __forceinline__ void put(Lds &L, Out &o, uint32_t v, uint32_t nb) {
 // (the header's "History"); without it `hist` is not looked at.  kGroups (with kHist): the launch is cut into
 // groups of `group` bytes, each a stream of its own whose tiles see only their group (the header's "Groups");
 // without it `group` is not looked at.
-template <int kLevel, bool kHist, bool kGroups = false>
+// kDeep (level 2 only): the walk's two limits are kernel arguments, `search` = depth | nice << 16 (the header's
+// "Search effort"); without it `search` is not looked at and the limits are kDepth and kNice.
+template <int kLevel, bool kHist, bool kGroups = false, bool kDeep = false>
 __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__ src, uint64_t n_bytes, uint32_t tile,
                                                      uint8_t *__restrict__ dst, uint32_t stride,
                                                      uint32_t *__restrict__ out_len, uint32_t *__restrict__ crc,
-                                                     uint32_t *__restrict__ scratch, uint32_t hist, uint32_t group) {
+                                                     uint32_t *__restrict__ scratch, uint32_t hist, uint32_t group,
+                                                     uint32_t search) {
     static_assert(kHist || !kGroups, "groups are built on the history's kernel");
+    static_assert(kLevel == 2 || !kDeep, "the search effort is level 2's");
     extern __shared__ __align__(16) uint8_t smem[];
     Lds &L = *reinterpret_cast<Lds *>(smem);
     uint32_t *T = L.tile;
@@ -493,7 +523,8 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
             if (cand && p >= skip) {
                 const uint32_t maxlen = m - p < kMaxMatch ? m - p : kMaxMatch;
                 uint32_t c = cand - 1u, best = 0, bestd = 0;
-                for (int k = 0; k < kDepth; ++k) {
+                // (kDeep: wave-uniform limits from the kernel argument, in place of the constants)
+                for (int k = 0; k < (kDeep ? (int)(search & 0xFFFFu) : kDepth); ++k) {
                     const uint32_t d = p - c;
                     if (d > kMaxDist || c + kLinks < base + 64u) break;
                     if (load32u(T, c) == v) {
@@ -511,7 +542,7 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
                             best = l;
                             bestd = d;
                         }
-                        if (best >= kNice || best >= maxlen) break;
+                        if (best >= (kDeep ? search >> 16 : kNice) || best >= maxlen) break;
                     }
                     const uint32_t back = link[c & (kLinks - 1u)];
                     if (!back || back > c) break;   // (back <= c: it points at a position of the tile)
@@ -767,9 +798,9 @@ uint64_t group_tiles(uint64_t n_bytes, uint32_t group, uint32_t tile) {
     return n_bytes / group * tpg + (rest + tile - 1) / tile;
 }
 
-template <int kLevel, bool kHist, bool kGroups = false>
+template <int kLevel, bool kHist, bool kGroups = false, bool kDeep = false>
 int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, uint8_t *dst, uint32_t stride, uint32_t *out_len,
-           uint32_t *crc, void *scratch, void *stream, uint32_t group = 0) {
+           uint32_t *crc, void *scratch, void *stream, uint32_t group = 0, uint32_t search = 0) {
     if (!tile || tile > kTileMax) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: tile must be 1..65536");
     if (stride < FC2_DEFLATE_TILE_BOUND(tile))
         return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: stride below FC2_DEFLATE_TILE_BOUND(tile)");
@@ -784,14 +815,14 @@ int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, u
     if (hipGetDevice(&dev) != hipSuccess) return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: no current device");
     const uint64_t bit = 1ull << (dev & 63);
     if (!(reserved.load() & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel<kLevel, kHist, kGroups>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel<kLevel, kHist, kGroups, kDeep>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kTileMax, kLevel)) != hipSuccess)
             return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: cannot reserve the kernel's LDS");
         reserved |= bit;
     }
-    hipLaunchKernelGGL((deflate_kernel<kLevel, kHist, kGroups>), dim3((uint32_t)tiles), dim3(64), lds_bytes(tile + hist, kLevel),
+    hipLaunchKernelGGL((deflate_kernel<kLevel, kHist, kGroups, kDeep>), dim3((uint32_t)tiles), dim3(64), lds_bytes(tile + hist, kLevel),
                        (hipStream_t)stream, src, n_bytes, tile, dst, stride, out_len, crc, static_cast<uint32_t *>(scratch),
-                       hist, group);
+                       hist, group, search);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? FC2_OK : fc2::fail(FC2_E_HIP, std::string("fc2_deflate_launch: ") + hipGetErrorString(e));
 }
@@ -841,4 +872,18 @@ extern "C" int fc2_deflate_launch_groups(const uint8_t *src, uint64_t n_bytes, u
                          "fc2_deflate_launch_groups: group must be >= 1, tile 1..65536, hist 0..32768, tile + hist <= 65536");
     if (level == 1) return launch<1, true, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, group);
     return launch<2, true, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, group);
+}
+
+extern "C" int fc2_deflate_launch_deep(const uint8_t *src, uint64_t n_bytes, uint32_t group, uint32_t tile, uint32_t hist,
+                                       uint8_t *dst, uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch,
+                                       void *stream, uint32_t depth, uint32_t nice) {
+    if (depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX || nice < FC2_DEFLATE_NICE_MIN ||
+        nice > FC2_DEFLATE_NICE_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_deep: depth is 1..128, nice 4..258");
+    if (!tile || tile > kTileMax || hist > kMaxDist || tile + hist > kTileMax)
+        return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_deep: tile must be 1..65536, hist 0..32768, tile + hist <= 65536");
+    const uint32_t search = depth | (nice << 16);
+    if (group) return launch<2, true, true, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, group, search);
+    if (hist) return launch<2, true, false, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, 0, search);
+    return launch<2, false, false, true>(src, n_bytes, tile, 0, dst, stride, out_len, crc, scratch, stream, 0, search);
 }

@@ -26,8 +26,10 @@ constexpr double kDefaultTimeout = 60.0;       // seconds a wait for the device 
 // fc2_deflate_launch_level); nullptr and err on failure.  hist > 0 (at most 32768, tile + hist <= 65536): a piece
 // is one launch of fc2_deflate_launch_hist -- every tile but the piece's first has the `hist` bytes before it as
 // its window -- and becomes one gzip member (fc2_gzmember_impl.h) instead of one per tile; pieces stay
-// independent of each other
-Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err);
+// independent of each other.  depth, nice (both 0: the level's own search): level 2's search effort,
+// fc2_deflate_launch_deep's depth 1..128 and nice 4..258 -- refused unless level is 2
+Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err,
+              uint32_t depth = 0, uint32_t nice = 0);
 // frees everything; a device that timed out is not waited for (its buffers are left to the process's end)
 void gpu_close(Gpu *g);
 size_t gpu_max_piece(const Gpu *g);

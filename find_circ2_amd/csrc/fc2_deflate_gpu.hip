@@ -42,6 +42,7 @@ struct Gpu {
     double timeout_s = kDefaultTimeout;
     int level = 1;
     uint32_t hist = 0;                         // > 0: fc2_deflate_launch_hist, and a piece is one member
+    uint32_t depth = 0, nice = 0;              // depth > 0: fc2_deflate_launch_deep with these (level 2 only)
     bool hung = false;                         // a wait timed out: the device is not touched again
     Slot slot[kSlots];
 };
@@ -52,9 +53,15 @@ static bool hip_ok(hipError_t e, const char *what, std::string &err) {
     return false;
 }
 
-Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err) {
+Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err,
+              uint32_t depth, uint32_t nice) {
     if (!tile || tile > 65536 || !max_piece || device < 0 || level < 1 || level > 2 || hist > 32768 || tile + hist > 65536) {
         err = "GPU gzip: bad tile, history, piece size, device or level";
+        return nullptr;
+    }
+    if ((depth || nice) && (level != 2 || depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX ||
+                            nice < FC2_DEFLATE_NICE_MIN || nice > FC2_DEFLATE_NICE_MAX)) {
+        err = "GPU gzip: the search effort needs level 2, depth 1..128 and nice 4..258";
         return nullptr;
     }
     Gpu *g = new Gpu();
@@ -65,6 +72,8 @@ Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int
     g->timeout_s = timeout_s > 0 ? timeout_s : kDefaultTimeout;
     g->level = level;
     g->hist = hist;
+    g->depth = depth;
+    g->nice = nice;
     g->max_tiles = (uint32_t)((max_piece + tile - 1) / tile);
     const size_t dst = (size_t)g->max_tiles * g->stride, meta = (size_t)g->max_tiles * 2 * sizeof(uint32_t);
     bool ok = hip_ok(hipSetDevice(device), "hipSetDevice", err);
@@ -131,8 +140,11 @@ bool gpu_submit(Gpu *g, int k, const char *data, size_t n, std::string &err) {
     s.busy = true;
     const bool ok =
         hip_ok(hipMemcpyAsync(s.d_src, s.h_src, n, hipMemcpyHostToDevice, s.stream), "upload", err) &&
-        (fc2_deflate_launch_hist(s.d_src, n, g->tile, g->hist, s.d_dst, g->stride, s.d_meta, s.d_meta + g->max_tiles,
-                                 s.d_scratch, s.stream, g->level) == FC2_OK || ((err = "GPU gzip: launch failed"), false)) &&
+        ((g->depth ? fc2_deflate_launch_deep(s.d_src, n, 0, g->tile, g->hist, s.d_dst, g->stride, s.d_meta,
+                                             s.d_meta + g->max_tiles, s.d_scratch, s.stream, g->depth, g->nice)
+                   : fc2_deflate_launch_hist(s.d_src, n, g->tile, g->hist, s.d_dst, g->stride, s.d_meta,
+                                             s.d_meta + g->max_tiles, s.d_scratch, s.stream, g->level)) == FC2_OK ||
+         ((err = "GPU gzip: launch failed"), false)) &&
         hip_ok(hipMemcpyAsync(s.h_dst, s.d_dst, (size_t)s.tiles * g->stride, hipMemcpyDeviceToHost, s.stream), "download", err) &&
         hip_ok(hipMemcpyAsync(s.h_meta, s.d_meta, s.tiles * w, hipMemcpyDeviceToHost, s.stream), "download", err) &&
         hip_ok(hipMemcpyAsync(s.h_meta + g->max_tiles, s.d_meta + g->max_tiles, s.tiles * w, hipMemcpyDeviceToHost, s.stream),
@@ -237,8 +249,27 @@ extern "C" int fc2_gpu_gzip_level(int device, const void *in, uint64_t n, uint32
     return fc2_gpu_gzip_hist(device, in, n, tile, 0, level, out, cap, out_n);
 }
 
+namespace {
+int gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, int level, uint32_t depth, uint32_t nice,
+             void *out, uint64_t cap, uint64_t *out_n);
+}  // namespace
+
 extern "C" int fc2_gpu_gzip_hist(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, int level, void *out,
                                  uint64_t cap, uint64_t *out_n) {
+    return gpu_gzip(device, in, n, tile, hist, level, 0, 0, out, cap, out_n);
+}
+
+extern "C" int fc2_gpu_gzip_deep(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, uint32_t depth,
+                                 uint32_t nice, void *out, uint64_t cap, uint64_t *out_n) {
+    if (depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX || nice < FC2_DEFLATE_NICE_MIN ||
+        nice > FC2_DEFLATE_NICE_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_gpu_gzip_deep: depth is 1..128, nice 4..258");
+    return gpu_gzip(device, in, n, tile, hist, 2, depth, nice, out, cap, out_n);
+}
+
+namespace {
+int gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, int level, uint32_t depth, uint32_t nice,
+             void *out, uint64_t cap, uint64_t *out_n) {
     using namespace fc2;
     if (!tile || tile > 65536 || device < 0 || !out || !out_n || (!in && n) || level < 1 || level > 2 || hist > 32768 ||
         tile + hist > 65536)
@@ -256,7 +287,7 @@ extern "C" int fc2_gpu_gzip_hist(int device, const void *in, uint64_t n, uint32_
     }
     const size_t piece = size_t(4) << 20;
     std::string err;
-    dgz::Gpu *g = dgz::gpu_open(device, piece, tile, 0, level, hist, err);
+    dgz::Gpu *g = dgz::gpu_open(device, piece, tile, 0, level, hist, err, depth, nice);
     if (!g) return fc2::fail(FC2_E_HIP, "fc2_gpu_gzip: " + err);
     const char *src = static_cast<const char *>(in);
     const uint64_t pieces = (n + piece - 1) / piece;
@@ -297,3 +328,4 @@ extern "C" int fc2_gpu_gzip_hist(int device, const void *in, uint64_t n, uint32_
     if (rc == FC2_OK) *out_n = at;
     return rc;
 }
+}  // namespace

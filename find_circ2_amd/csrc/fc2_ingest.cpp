@@ -643,6 +643,7 @@ struct fc2_ingest {
     uint64_t bam_gpu_pieces = 0, bam_cpu_pieces = 0;    // fc2_ingest_bam_out_counts, once the writer is closed
     int bam_level = 1;                          // fc2_ingest_set_bam_out_device_level
     uint32_t bam_tile = 0, bam_hist = 0;        // fc2_ingest_set_bam_out_device_tiles
+    uint32_t bam_depth = 0, bam_nice = 0;       // fc2_ingest_set_bam_out_device_search (0, 0: the level's own)
     // grouping state
     bool started = false;
     Mate current, other;
@@ -2406,9 +2407,11 @@ extern "C" int fc2_ingest_set_bam_out_device(fc2_ingest *h, int mode, int device
     if (mode && tile && tile < cut && ((cut - 1) / tile + 1 > 16 || tile + h->bam_hist > 65536))
         return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: at most 16 tiles a block, and tile and history at most "
                                       "65536 bytes together");
+    if (mode && h->bam_depth && h->bam_level != 2)
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: the search effort needs level 2");
     std::string err;
     if (!fc2::bam::set_device(h->bam_out, mode, device, block, piece_blocks, timeout_s, h->bam_level, h->bam_tile,
-                              h->bam_hist, err))
+                              h->bam_hist, err, h->bam_depth, h->bam_nice))
         return fc2::fail(mode == 1 ? FC2_E_HIP : FC2_E_PARAM, "fc2_ingest_set_bam_out_device: " + err);
     return FC2_OK;
 }
@@ -2431,6 +2434,22 @@ extern "C" int fc2_ingest_set_bam_out_device_level(fc2_ingest *h, int level) {
                                       "fc2_ingest_set_bam_out_device and before reading");
     if (level < 1 || level > 2) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_level: level is 1 or 2");
     h->bam_level = level;
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_set_bam_out_device_search(fc2_ingest *h, uint32_t depth, uint32_t nice) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_search: null argument");
+    if (!h->bam_out || h->n_records || fc2::bam::device_set(h->bam_out))
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_search: call after fc2_ingest_set_bam_out, before "
+                                      "fc2_ingest_set_bam_out_device and before reading");
+    if (depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX || nice < FC2_DEFLATE_NICE_MIN ||
+        nice > FC2_DEFLATE_NICE_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_search: depth is 1..128, nice 4..258");
+    if (h->bam_level != 2)
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_search: set level 2 first "
+                                      "(fc2_ingest_set_bam_out_device_level)");
+    h->bam_depth = depth;
+    h->bam_nice = nice;
     return FC2_OK;
 }
 

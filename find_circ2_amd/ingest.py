@@ -134,11 +134,20 @@ class NativeIngest:
             pass
 
 
+def _u32(v, default: int) -> int:
+    """``v`` (None: ``default``) as the library takes a uint32_t: anything outside it becomes 0xFFFFFFFF, which
+    every range check refuses, instead of wrapping into the range."""
+    v = default if v is None else int(v)
+    return v if 0 <= v <= 0xFFFFFFFF else 0xFFFFFFFF
+
+
 def set_bam_out_device(h, bam_device) -> None:
     """fc2_ingest_set_bam_out_device on the ingest handle ``h`` (NativeIngest.set_bam_out's bam_device)."""
     d = dict(bam_device)
     if int(d.get("level", 1)) != 1:
         N.check(N.lib().fc2_ingest_set_bam_out_device_level(h, int(d["level"])))
+    if d.get("depth") is not None or d.get("nice") is not None:     # level 2's search effort (else its own 8 and 32)
+        N.check(N.lib().fc2_ingest_set_bam_out_device_search(h, _u32(d.get("depth"), 8), _u32(d.get("nice"), 32)))
     if int(d.get("tile", 0)) or int(d.get("hist", 0)):
         N.check(N.lib().fc2_ingest_set_bam_out_device_tiles(h, int(d.get("tile", 0)), int(d.get("hist", 0))))
     N.check(N.lib().fc2_ingest_set_bam_out_device(h, int(d.get("mode", 1)), int(d.get("device", 0)), int(d.get("block", 0)),

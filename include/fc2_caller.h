@@ -138,6 +138,13 @@ int fc2_caller_set_reads_gz_device_level(fc2_caller *h, int level);
  * are refused by fc2_caller_set_reads_gz_device itself (FC2_E_PARAM), which then leaves the CPU writer in place.
  * The command line passes FC2_GPU_GZIP_HISTORY here. */
 int fc2_caller_set_reads_gz_device_history(fc2_caller *h, uint32_t hist);
+/* This handle's search effort at level 2 on the device (fc2_deflate_launch_deep's depth 1..128 and nice 4..258; not
+ * called: level 2's own 8 and 32), for the device mode set afterwards with fc2_caller_set_reads_gz_device.  Call
+ * after fc2_caller_set_reads_gz_device_level(h, 2): FC2_E_PARAM while the level is 1, for a value out of range and
+ * for a call after fc2_caller_set_reads_gz_device.  If the level is set back to 1 afterwards,
+ * fc2_caller_set_reads_gz_device itself is refused (FC2_E_PARAM).  The command line passes FC2_GPU_GZIP_DEPTH and
+ * FC2_GPU_GZIP_NICE here. */
+int fc2_caller_set_reads_gz_device_search(fc2_caller *h, uint32_t depth, uint32_t nice);
 /* pieces the device compressed, and pieces of the device mode the CPU compressed, so far (0, 0 without it) */
 int fc2_caller_reads_gz_counts(const fc2_caller *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces);
 
@@ -184,6 +191,17 @@ int fc2_deflate_launch_groups(const uint8_t *src, uint64_t n_bytes, uint32_t gro
                               void *stream, int level);
 /* tiles of fc2_deflate_launch_groups over n_bytes (0 for group 0 or a tile outside 1..65536) */
 uint64_t fc2_deflate_group_tiles(uint64_t n_bytes, uint32_t group, uint32_t tile);
+/* Level 2 with its search effort as arguments: `depth`, the candidates a position walks at most (level 2 itself: 8),
+ * and `nice`, the kept length that ends the walk (level 2 itself: 32).  Everything else of level 2 -- the links, the
+ * ends of the walk, the first among equal lengths, the cost rule, the lazy step, the stream -- is unchanged, and at
+ * depth 8, nice 32 every byte is the matching existing entry's at level 2.  group = 0: fc2_deflate_launch_hist's
+ * shape (hist = 0: independent tiles, fc2_deflate_launch_level's); group >= 1: fc2_deflate_launch_groups' shape.
+ * Same slots, scratch and bound.  depth outside 1..128 or nice outside 4..258 is FC2_E_PARAM before the device is
+ * touched, as is everything the existing entries refuse.  (FC2_DEFLATE_DEPTH_MIN .. FC2_DEFLATE_NICE_MAX:
+ * include/fc2_ingest.h.) */
+int fc2_deflate_launch_deep(const uint8_t *src, uint64_t n_bytes, uint32_t group, uint32_t tile, uint32_t hist,
+                            uint8_t *dst, uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch,
+                            void *stream, uint32_t depth, uint32_t nice);
 /* one buffer through the host path of spliced_reads.fastq.gz's device mode, for tests and other hosts: gzip
  * members (one per tile) of in[0, n) into out (cap bytes); FC2_E_RANGE if they do not fit. */
 int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, void *out, uint64_t cap, uint64_t *out_n);
@@ -194,6 +212,11 @@ int fc2_gpu_gzip_level(int device, const void *in, uint64_t n, uint32_t tile, in
  * gzip member, its tiles' streams back to back (csrc/fc2_gzmember_impl.h).  hist = 0: fc2_gpu_gzip_level's bytes. */
 int fc2_gpu_gzip_hist(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, int level, void *out,
                       uint64_t cap, uint64_t *out_n);
+/* fc2_gpu_gzip_hist at level 2 with fc2_deflate_launch_deep's search effort (depth 1..128, nice 4..258, else
+ * FC2_E_PARAM before the device is touched); depth 8, nice 32: fc2_gpu_gzip_hist's bytes at level 2.
+ * fc2_gpu_gzip_bound holds. */
+int fc2_gpu_gzip_deep(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, uint32_t depth, uint32_t nice,
+                      void *out, uint64_t cap, uint64_t *out_n);
 uint64_t fc2_gpu_gzip_bound(uint64_t n, uint32_t tile);
 
 /* ---- BGZF output on the GPU (csrc/fc2_bgzf_out.hip; the rule: csrc/fc2_bgzf_frame_impl.h) ---- */
@@ -226,6 +249,11 @@ int fc2_gpu_bgzf_level(int device, const void *in, uint64_t n, uint32_t block, u
  * 0..32768, tile + hist <= 65536, else FC2_E_PARAM.  tile = 0 or tile >= block: fc2_gpu_bgzf_level's bytes. */
 int fc2_gpu_bgzf_tiles(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
                        uint32_t hist, int level, void *out, uint64_t cap, uint64_t *out_n);
+/* fc2_gpu_bgzf_tiles at level 2 with fc2_deflate_launch_deep's search effort (depth 1..128, nice 4..258, else
+ * FC2_E_PARAM before the device is touched); depth 8, nice 32: fc2_gpu_bgzf_tiles' bytes at level 2.  The ISIZE
+ * values do not depend on the search; fc2_gpu_bgzf_tiles_bound holds. */
+int fc2_gpu_bgzf_deep(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
+                      uint32_t hist, uint32_t depth, uint32_t nice, void *out, uint64_t cap, uint64_t *out_n);
 /* the bytes fc2_gpu_bgzf_tiles needs at most: fc2_gpu_bgzf_bound's with every tile's stream at its worst */
 uint64_t fc2_gpu_bgzf_tiles_bound(uint64_t n, uint32_t block, uint32_t tile);
 uint64_t fc2_gpu_bgzf_bound(uint64_t n, uint32_t block);

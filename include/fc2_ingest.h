@@ -100,6 +100,19 @@ int fc2_ingest_set_bam_out_device(fc2_ingest *h, int mode, int device, uint32_t 
  * device mode set afterwards with fc2_ingest_set_bam_out_device; mode 2 ignores it.  FC2_E_PARAM for another
  * level or a call after reading has begun.  The command line passes FC2_GPU_BAM_LEVEL here. */
 int fc2_ingest_set_bam_out_device_level(fc2_ingest *h, int level);
+/* the ranges of level 2's search effort on the device (fc2_deflate_launch_deep, include/fc2_caller.h): the candidates
+ * a position walks at most, and the kept match length that ends the walk */
+#define FC2_DEFLATE_DEPTH_MIN 1u
+#define FC2_DEFLATE_DEPTH_MAX 128u
+#define FC2_DEFLATE_NICE_MIN 4u
+#define FC2_DEFLATE_NICE_MAX 258u
+/* The search effort mode 1 compresses with at level 2 (not called: level 2's own depth 8 and nice 32), for the device
+ * mode set afterwards with fc2_ingest_set_bam_out_device; mode 2 ignores it as it ignores the level.  Call where
+ * fc2_ingest_set_bam_out_device_level is called, after it has set level 2: FC2_E_PARAM while the level is 1, for a
+ * value out of range, and for a call before fc2_ingest_set_bam_out, after fc2_ingest_set_bam_out_device or after
+ * reading has begun.  If the level is set back to 1 afterwards, fc2_ingest_set_bam_out_device itself is refused
+ * (FC2_E_PARAM).  The command line passes FC2_GPU_BAM_DEPTH and FC2_GPU_BAM_NICE here. */
+int fc2_ingest_set_bam_out_device_search(fc2_ingest *h, uint32_t depth, uint32_t nice);
 /* Tiles inside a block, for the device mode set afterwards with fc2_ingest_set_bam_out_device: every block of the
  * record bytes is cut into tiles of `tile` bytes, each compressed by a wavefront of its own with the min(hist,
  * its offset in the block) bytes of its block before it as history, and the block's streams, combined CRC-32 and
