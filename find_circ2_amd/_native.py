@@ -161,6 +161,7 @@ EXPORTED = [
     "fc2_bam_frag_launch", "fc2_bam_frag_host", "fc2_ingest_set_gpu_group", "fc2_ingest_group_counts",
     "fc2_ingest_set_bam_out_device", "fc2_ingest_set_bam_out_device_level", "fc2_ingest_bam_out_counts",
     "fc2_ingest_set_bam_out_device_tiles", "fc2_ingest_set_bam_out_device_search",
+    "fc2_ingest_set_bam_out_device_passes",
     # include/fc2_caller.h
     "fc2_caller_open", "fc2_caller_set_genome", "fc2_caller_inflate_counts", "fc2_caller_ingest", "fc2_caller_close", "fc2_caller_next",
     "fc2_caller_submit", "fc2_caller_submit_compact", "fc2_caller_submit_long", "fc2_caller_queued", "fc2_caller_take", "fc2_caller_rows", "fc2_caller_write_rows", "fc2_caller_counter", "fc2_caller_stats",
@@ -172,6 +173,7 @@ EXPORTED = [
     "fc2_deflate_launch_groups", "fc2_deflate_group_tiles", "fc2_bgzf_frame_groups_launch", "fc2_bgzf_frame_groups_host",
     "fc2_gpu_bgzf_tiles", "fc2_gpu_bgzf_tiles_bound",
     "fc2_deflate_launch_deep", "fc2_gpu_gzip_deep", "fc2_gpu_bgzf_deep", "fc2_caller_set_reads_gz_device_search",
+    "fc2_deflate_launch_priced", "fc2_gpu_gzip_priced", "fc2_gpu_bgzf_priced", "fc2_caller_set_reads_gz_device_passes",
     # include/fc2_ctx.h
     "fc2_ctx_create", "fc2_ctx_create_sibling", "fc2_ctx_destroy", "fc2_ctx_genome_load", "fc2_ctx_genome_view", "fc2_ctx_scan_async",
     "fc2_ctx_sync", "fc2_ctx_scan_long", "fc2_ctx_stream", "fc2_ctx_last_error",
@@ -377,6 +379,11 @@ def lib() -> ctypes.CDLL:
         "fc2_gpu_bgzf_deep": (ctypes.c_int, [ctypes.c_int, vp, u64, u32, u32, u32, u32, u32, u32, vp, u64, P(u64)]),
         "fc2_caller_set_reads_gz_device_search": (ctypes.c_int, [vp, u32, u32]),
         "fc2_ingest_set_bam_out_device_search": (ctypes.c_int, [vp, u32, u32]),
+        "fc2_deflate_launch_priced": (ctypes.c_int, [vp, u64, u32, u32, u32, vp, u32, vp, vp, vp, vp, u32, u32, u32]),
+        "fc2_gpu_gzip_priced": (ctypes.c_int, [ctypes.c_int, vp, u64, u32, u32, u32, u32, u32, vp, u64, P(u64)]),
+        "fc2_gpu_bgzf_priced": (ctypes.c_int, [ctypes.c_int, vp, u64, u32, u32, u32, u32, u32, u32, u32, vp, u64, P(u64)]),
+        "fc2_caller_set_reads_gz_device_passes": (ctypes.c_int, [vp, u32]),
+        "fc2_ingest_set_bam_out_device_passes": (ctypes.c_int, [vp, u32]),
         "fc2_ingest_bam_out_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "fc2_ctx_create": (ctypes.c_int, [ctypes.c_int, P(vp)]),
         "fc2_ctx_create_sibling": (ctypes.c_int, [vp, P(vp)]),

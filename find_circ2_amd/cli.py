@@ -317,6 +317,17 @@ def _search_note(tag, search) -> str:
     return ", %s_gpu_depth=%d, %s_gpu_nice=%d" % (tag, search[0], tag, search[1]) if search else ""
 
 
+def _passes_env(prefix):
+    """Level 2's passes from ``prefix``_PASSES (DESIGN.md §5 "Priced passes at level 2"), or None with it unset or
+    empty: one pass.  The library judges the value (1..3), and that level 2 is set."""
+    passes = os.environ.get(prefix + "_PASSES")
+    return int(passes) if passes else None
+
+
+def _passes_note(tag, passes) -> str:
+    return ", %s_gpu_passes=%d" % (tag, passes) if passes is not None and passes > 1 else ""
+
+
 def _gzip_device(options):
     """spliced_reads.fastq.gz compressed on the GPU: only with FC2_GPU_GZIP=1, on the first of
     the run's devices, in tiles of FC2_GPU_GZIP_TILE bytes (32768), waiting at most
@@ -324,7 +335,8 @@ def _gzip_device(options):
     (unset or anything else: level 1), every tile referring to the FC2_GPU_GZIP_HISTORY bytes of its piece
     before it (unset, empty or 0: none; DESIGN.md §5 "History across the tiles"), level 2 searching with
     FC2_GPU_GZIP_DEPTH candidates (1..128) up to a length of FC2_GPU_GZIP_NICE (4..258; both unset or empty: its
-    own 8 and 32; without FC2_GPU_GZIP_LEVEL=2 or out of range the library refuses them and the run ends).
+    own 8 and 32; without FC2_GPU_GZIP_LEVEL=2 or out of range the library refuses them and the run ends), parsing
+    every tile FC2_GPU_GZIP_PASSES times (1..3; unset or empty: once; refused like the two before).
     Anything but 1: {}, the worker threads compress and none of these is read."""
     if os.environ.get("FC2_GPU_GZIP") != "1":
         return {}
@@ -332,7 +344,8 @@ def _gzip_device(options):
     return dict(gzip_device=device_index(options.device), gzip_tile=int(os.environ.get("FC2_GPU_GZIP_TILE") or 0),
                 gzip_timeout_s=float(os.environ.get("FC2_GPU_GZIP_TIMEOUT_S") or 0),
                 gzip_level=2 if os.environ.get("FC2_GPU_GZIP_LEVEL") == "2" else 1,
-                gzip_history=int(os.environ.get("FC2_GPU_GZIP_HISTORY") or 0), gzip_search=_search_env("FC2_GPU_GZIP"))
+                gzip_history=int(os.environ.get("FC2_GPU_GZIP_HISTORY") or 0), gzip_search=_search_env("FC2_GPU_GZIP"),
+                gzip_passes=_passes_env("FC2_GPU_GZIP"))
 
 
 def _bam_device(options):
@@ -343,16 +356,18 @@ def _bam_device(options):
     FC2_GPU_BAM_HISTORY bytes (0..32768; unset, empty or 0: none) of their block before them (DESIGN.md §5
     "Tiles inside a BGZF block"), level 2 searching with FC2_GPU_BAM_DEPTH candidates (1..128) up to a length of
     FC2_GPU_BAM_NICE (4..258; both unset or empty: its own 8 and 32; without FC2_GPU_BAM_LEVEL=2 or out of range
-    the library refuses them and the run ends).  Unset, 0 or anything else: None, zlib compresses on the reading
+    the library refuses them and the run ends), parsing every tile FC2_GPU_BAM_PASSES times (1..3; unset or empty:
+    once; refused like the two before).  Unset, 0 or anything else: None, zlib compresses on the reading
     thread, and none of these is read."""
     if os.environ.get("FC2_GPU_BAM") != "1":
         return None
     from .ctxpipe import device_index
-    search = _search_env("FC2_GPU_BAM")
+    search, passes = _search_env("FC2_GPU_BAM"), _passes_env("FC2_GPU_BAM")
     return dict(mode=1, device=device_index(options.device), timeout_s=float(os.environ.get("FC2_GPU_BAM_TIMEOUT_S") or 0),
                 level=2 if os.environ.get("FC2_GPU_BAM_LEVEL") == "2" else 1,
                 tile=int(os.environ.get("FC2_GPU_BAM_TILE") or 0), hist=int(os.environ.get("FC2_GPU_BAM_HISTORY") or 0),
-                **(dict(depth=search[0], nice=search[1]) if search else {}))
+                **(dict(depth=search[0], nice=search[1]) if search else {}),
+                **(dict(passes=passes) if passes is not None else {}))
 
 
 def _bam_tiles_note(bam_device) -> str:
@@ -451,7 +466,9 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                 (", bam_gpu_level=2" if nc.bam_device and nc.bam_device.get("level") == 2 else "") + _bam_tiles_note(nc.bam_device) + \
                 _search_note("gzip", nc.gzip_search if nc.gzip_device is not None else None) + \
                 _search_note("bam", (nc.bam_device["depth"], nc.bam_device["nice"])
-                             if nc.bam_device and nc.bam_device.get("depth") is not None else None)
+                             if nc.bam_device and nc.bam_device.get("depth") is not None else None) + \
+                _passes_note("gzip", nc.gzip_passes if nc.gzip_device is not None else None) + \
+                _passes_note("bam", nc.bam_device.get("passes") if nc.bam_device else None)
             logger.info("process phases: " + ", ".join("%s=%.3f" % kv for kv in startup.items()) + levels +
                         ", process_age_s=%.3f, numpy_loaded=%d, torch_loaded=%d"
                         % (process_age(), "numpy" in sys.modules, "torch" in sys.modules))

@@ -468,7 +468,7 @@ bool encode_sam(const char *line, const char *end, const std::unordered_map<std:
 bool device_set(const Writer *w) { return w && w->mode != 0; }
 
 bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level,
-                uint32_t tile, uint32_t hist, std::string &err, uint32_t depth, uint32_t nice) {
+                uint32_t tile, uint32_t hist, std::string &err, uint32_t depth, uint32_t nice, uint32_t passes) {
     if (!block) block = bgz::kDefaultBlock;
     if (!piece_blocks) piece_blocks = bgz::kDefaultPieceBlocks;
     if (!w || mode < 0 || mode > 2 || block > kBlockIn || piece_blocks > bgz::kMaxPieceBlocks || timeout_s < 0 ||
@@ -486,12 +486,16 @@ bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_
         err = "the search effort needs level 2, depth 1..128 and nice 4..258";
         return false;
     }
+    if (passes && (level != 2 || passes < FC2_DEFLATE_PASSES_MIN || passes > FC2_DEFLATE_PASSES_MAX)) {
+        err = "the passes need level 2 and are 1..3";
+        return false;
+    }
     if (tile >= block) tile = 0;                // (a block is one tile)
     if (tile && (hist > 32768u || tile + hist > 65536u || (block - 1) / tile + 1 > 16)) {
         err = "at most 16 tiles a block, a history of at most 32768 bytes, tile and history at most 65536 together";
         return false;
     }
-    if (mode == 1 && !(w->gpu = bgz::gpu_open(device, block, piece_blocks, timeout_s, level == 2 && depth ? bgz::level_with_search(depth, nice) : level,
+    if (mode == 1 && !(w->gpu = bgz::gpu_open(device, block, piece_blocks, timeout_s, level == 2 && (depth || passes > 1) ? bgz::level_with_search(depth, nice, passes) : level,
                                               tile, hist, err)))
         return false;
     w->mode = mode;

@@ -43,9 +43,9 @@ bool write_bulk(Writer *w, const char *p, size_t n, int threads);
 // block before it as history (fc2_deflate_launch_groups, fc2_bgzf_frame_groups_launch; mode 2: zlib flushed
 // at the tiles' ends and fc2_bgzf_frame_groups_host); more than 16 tiles a block, hist over 32768 or tile + hist
 // over 65536 are refused.  depth, nice (0, 0: the level's own): level 2's search effort on the device
-// (bgz::gpu_open); mode 2 ignores them as it ignores the level.
+// (bgz::gpu_open); passes (0: one): level 2's passes on the device, 1..3; mode 2 ignores them as it ignores the level.
 bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level,
-                uint32_t tile, uint32_t hist, std::string &err, uint32_t depth = 0, uint32_t nice = 0);
+                uint32_t tile, uint32_t hist, std::string &err, uint32_t depth = 0, uint32_t nice = 0, uint32_t passes = 0);
 bool device_set(const Writer *w);              // set_device has put the writer into mode 1 or 2
 // pieces written from the device (or the host model), and pieces of the device mode zlib compressed, so far
 void device_counts(const Writer *w, uint64_t &gpu_pieces, uint64_t &cpu_pieces);

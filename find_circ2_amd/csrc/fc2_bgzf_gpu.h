@@ -30,13 +30,18 @@ constexpr double kDefaultTimeout = 60.0;       // seconds a wait for the device 
 // fc2_deflate_launch_groups fills piece_blocks * ceil(block / tile) slots and fc2_bgzf_frame_groups_launch packs
 // each block's streams, its combined CRC-32 and ISIZE into one BGZF block; the rest is the same.  `level` may
 // carry level 2's search effort (fc2_deflate_launch_deep's depth 1..128 and nice 4..258) as level_with_search(depth,
-// nice) gives it; a plain 1 or 2 is the level's own search.  (Both travel in the one argument so that gpu_open
-// keeps the signature its callers and stand-ins are written against.)
+// nice) gives it; a plain 1 or 2 is the level's own search.  level_with_search(depth, nice, passes) adds level 2's
+// passes (fc2_deflate_launch_priced's 1..3), with that search effort or, depth 0, level 2's own.  (All travel in the
+// one argument so that gpu_open keeps the signature its callers and stand-ins are written against.)
 Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level, uint32_t tile, uint32_t hist,
               std::string &err);
 // level 2 with its search effort for gpu_open's `level`: depth in bits 8..15, nice in bits 16..24 (depth 0: plain 2)
 constexpr int level_with_search(uint32_t depth, uint32_t nice) {
     return depth ? (int)(2u | (depth & 0xFFu) << 8 | (nice & 0x1FFu) << 16) : 2;
+}
+// ... and its passes in bits 25..26 (0 and 1: one pass, the word above)
+constexpr int level_with_search(uint32_t depth, uint32_t nice, uint32_t passes) {
+    return level_with_search(depth, nice) | (int)((passes > 1u ? passes & 3u : 0u) << 25);
 }
 // frees everything; a device that timed out is not waited for (its buffers are left to the process's end)
 void gpu_close(Gpu *g);

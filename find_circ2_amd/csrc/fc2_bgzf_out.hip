@@ -350,6 +350,7 @@ struct Gpu {
     int level = 1;                             // fc2_deflate_launch_level's
     uint32_t tile = 0, hist = 0, tpg = 1;      // tile > 0: blocks of tpg tiles (fc2_deflate_launch_groups); 0: a block is a tile
     uint32_t depth = 0, nice = 0;              // depth > 0: fc2_deflate_launch_deep with these (level 2 only)
+    uint32_t passes = 0;                       // > 1: fc2_deflate_launch_priced with these (level 2 only)
     bool hung = false;                         // a wait timed out: the device is not touched again
     Slot slot[kSlots];
 };
@@ -385,9 +386,10 @@ static Wait wait_event(Gpu *g, Slot &s, std::string &err) {
 
 Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_s, int level, uint32_t tile, uint32_t hist,
               std::string &err) {
-    // (level_with_search: level 2's search effort rides in the level's upper bits)
+    // (level_with_search: level 2's search effort and passes ride in the level's upper bits)
     const uint32_t depth = ((uint32_t)level >> 8) & 0xFFu, nice = ((uint32_t)level >> 16) & 0x1FFu;
-    if (level > 0 && (depth || nice)) level &= 0xFF;
+    const uint32_t passes = ((uint32_t)level >> 25) & 3u;
+    if (level > 0 && (depth || nice || passes)) level &= 0xFF;
     if (!block || block > bgzf::kTileMax || !piece_blocks || piece_blocks > kMaxPieceBlocks || device < 0 || level < 1 ||
         level > 2) {
         err = "GPU BGZF: bad block size, piece size, device or level";
@@ -396,6 +398,10 @@ Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_
     if ((depth || nice) && (level != 2 || depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX ||
                             nice < FC2_DEFLATE_NICE_MIN || nice > FC2_DEFLATE_NICE_MAX)) {
         err = "GPU BGZF: the search effort needs level 2, depth 1..128 and nice 4..258";
+        return nullptr;
+    }
+    if (passes && level != 2) {
+        err = "GPU BGZF: passes need level 2";
         return nullptr;
     }
     if (tile >= block) tile = 0;                // (a block is one tile: today's launches, and no history to have)
@@ -417,6 +423,7 @@ Gpu *gpu_open(int device, uint32_t block, uint32_t piece_blocks, double timeout_
     g->timeout_s = timeout_s > 0 ? timeout_s : kDefaultTimeout;
     g->level = level;
     g->depth = depth;
+    g->passes = passes;
     g->nice = nice;
     const size_t slots = (size_t)g->max_tiles * g->stride, meta = ((size_t)g->max_tiles * 3 + 2) * sizeof(uint32_t),
                  scratch = (size_t)fc2_deflate_scratch_bytes(g->max_piece, tile ? tile : block);
@@ -488,6 +495,11 @@ bool gpu_submit(Gpu *g, int k, const char *data, size_t n, std::string &err) {
     // counts as busy, and a failure drains the stream before the slot's buffers can be used again)
     s.busy = true;
     auto compress = [&] {
+        if (g->passes > 1)                      // (level 2's own search where none is set)
+            return fc2_deflate_launch_priced(s.d_src, n, g->tile ? g->block : 0, g->tile ? g->tile : g->block, g->hist, s.d_slots,
+                                             g->stride, d_len, d_crc, s.d_scratch, s.stream,
+                                             g->depth ? g->depth : FC2_DEFLATE_LEVEL2_DEPTH,
+                                             g->depth ? g->nice : FC2_DEFLATE_LEVEL2_NICE, g->passes);
         if (g->depth)                           // (group = block: one tile a block is fc2_deflate_launch_level's shape)
             return fc2_deflate_launch_deep(s.d_src, n, g->tile ? g->block : 0, g->tile ? g->tile : g->block, g->hist, s.d_slots,
                                            g->stride, d_len, d_crc, s.d_scratch, s.stream, g->depth, g->nice);
@@ -625,7 +637,7 @@ extern "C" int fc2_gpu_bgzf_level(int device, const void *in, uint64_t n, uint32
 
 namespace {
 int gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile, uint32_t hist, int level,
-             uint32_t depth, uint32_t nice, void *out, uint64_t cap, uint64_t *out_n);
+             uint32_t depth, uint32_t nice, void *out, uint64_t cap, uint64_t *out_n, uint32_t passes = 0);
 }  // namespace
 
 extern "C" int fc2_gpu_bgzf_tiles(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
@@ -641,9 +653,20 @@ extern "C" int fc2_gpu_bgzf_deep(int device, const void *in, uint64_t n, uint32_
     return gpu_bgzf(device, in, n, block, piece_blocks, tile, hist, 2, depth, nice, out, cap, out_n);
 }
 
+extern "C" int fc2_gpu_bgzf_priced(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
+                                   uint32_t hist, uint32_t depth, uint32_t nice, uint32_t passes, void *out, uint64_t cap,
+                                   uint64_t *out_n) {
+    if (passes < FC2_DEFLATE_PASSES_MIN || passes > FC2_DEFLATE_PASSES_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_gpu_bgzf_priced: passes is 1..3");
+    if (depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX || nice < FC2_DEFLATE_NICE_MIN ||
+        nice > FC2_DEFLATE_NICE_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_gpu_bgzf_priced: depth is 1..128, nice 4..258");
+    return gpu_bgzf(device, in, n, block, piece_blocks, tile, hist, 2, depth, nice, out, cap, out_n, passes);
+}
+
 namespace {
 int gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile, uint32_t hist, int level,
-             uint32_t depth, uint32_t nice, void *out, uint64_t cap, uint64_t *out_n) {
+             uint32_t depth, uint32_t nice, void *out, uint64_t cap, uint64_t *out_n, uint32_t passes) {
     using namespace fc2;
     if (!block || block > kTileMax || piece_blocks > bgz::kMaxPieceBlocks || device < 0 || !out || !out_n || (!in && n) ||
         level < 1 || level > 2)
@@ -654,7 +677,7 @@ int gpu_bgzf(int device, const void *in, uint64_t n, uint32_t block, uint32_t pi
     if (!n) return FC2_OK;
     if (!piece_blocks) piece_blocks = bgz::kDefaultPieceBlocks;
     std::string err;
-    bgz::Gpu *g = bgz::gpu_open(device, block, piece_blocks, 0, depth ? bgz::level_with_search(depth, nice) : level, tile, hist, err);
+    bgz::Gpu *g = bgz::gpu_open(device, block, piece_blocks, 0, depth ? bgz::level_with_search(depth, nice, passes) : level, tile, hist, err);
     if (!g) return fc2::fail(FC2_E_HIP, "fc2_gpu_bgzf: " + err);
     const char *src = static_cast<const char *>(in);
     uint8_t *o = static_cast<uint8_t *>(out);

@@ -891,6 +891,7 @@ struct fc2_caller {
     int gz_level = 1;                           // fc2_caller_set_reads_gz_device_level
     uint32_t gz_hist = 0;                       // fc2_caller_set_reads_gz_device_history
     uint32_t gz_depth = 0, gz_nice = 0;         // fc2_caller_set_reads_gz_device_search (0, 0: the level's own)
+    uint32_t gz_passes = 0;                     // fc2_caller_set_reads_gz_device_passes (0: one)
     uint64_t n_chunks = 0;                      // chunks formed (next side)
 };
 
@@ -2710,7 +2711,10 @@ extern "C" int fc2_caller_set_reads_gz_device(fc2_caller *h, int device) {
         return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: tile + history over 65536 (the CPU writer stays)");
     if (h->gz_depth && h->gz_level != 2)
         return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: the search effort needs level 2 (the CPU writer stays)");
-    if (!h->reads_gz.set_device(device, h->gz_tile, h->gz_timeout_s, h->gz_level, h->gz_hist, err, h->gz_depth, h->gz_nice))
+    if (h->gz_passes && h->gz_level != 2)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device: the passes need level 2 (the CPU writer stays)");
+    if (!h->reads_gz.set_device(device, h->gz_tile, h->gz_timeout_s, h->gz_level, h->gz_hist, err, h->gz_depth, h->gz_nice,
+                                h->gz_passes))
         return fc2::fail(FC2_E_HIP, "fc2_caller_set_reads_gz_device: " + err);
     return FC2_OK;
 }
@@ -2744,6 +2748,17 @@ extern "C" int fc2_caller_set_reads_gz_device_search(fc2_caller *h, uint32_t dep
         return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_search: set level 2 first (fc2_caller_set_reads_gz_device_level)");
     h->gz_depth = depth;
     h->gz_nice = nice;
+    return FC2_OK;
+}
+
+extern "C" int fc2_caller_set_reads_gz_device_passes(fc2_caller *h, uint32_t passes) {
+    if (!h || passes < FC2_DEFLATE_PASSES_MIN || passes > FC2_DEFLATE_PASSES_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_passes: null handle, or not passes 1..3");
+    if (h->reads_gz.device_mode())
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_passes: call before fc2_caller_set_reads_gz_device");
+    if (h->gz_level != 2)
+        return fc2::fail(FC2_E_PARAM, "fc2_caller_set_reads_gz_device_passes: set level 2 first (fc2_caller_set_reads_gz_device_level)");
+    h->gz_passes = passes;
     return FC2_OK;
 }
 

@@ -143,6 +143,51 @@
 //   Instantiations.  The six kernels above got one more unread kernel argument (`search`); their instructions are
 // those of before, compared in the compiler's output (one symbol's name differs).  Resource report for gfx950
 // as above:   <2, false, false, true> 48, 76, 0    <2, true, false, true> 47, 82, 0    <2, true, true, true> 47, 82, 0
+//
+// Priced passes (deflate_kernel<2, .., .., true, true>, fc2_deflate_launch_priced; tests/deflate_model_priced.py is the
+// rule in Python).  The search above run 2 or 3 times over the same region, every pass after the first judging a match
+// by the Huffman code the pass before it produced.  `search` carries the number too: depth | nice << 16 | passes << 28
+// (depth <= 128 and nice <= 258 leave bits 25..31 free), wave-uniform like the other two.
+//   Pass 1 is the search effort's pass 1, lit16 and all.  After a pass that is not the last: lfreq[256] = 1, then
+// build_code(lfreq, 286, 15) and build_code(dfreq, 30, 15) exactly as they run after the last pass -- dummy symbols,
+// overflow repair -- but no code-length code and no header.  If either is not ok (not expected) no further pass runs
+// and the tile goes on below with the tokens it has.  Else the heads are zeroed (the code builder's workspace lay in
+// them), the two histograms are zeroed, ntok = 0, extra = 0, skip = h, and the pass loop runs again from base = 0,
+// writing its tokens over the scratch: the last pass's tokens are the ones emitted, nothing compares passes, and the
+// stored form still bounds the tile.
+//   The one difference of a pass k >= 2 is the cost rule.  With llen and dlen as the last build_code left them,
+// lit(b) = llen[b], or 15 where that is 0; match(l, d) = (llen[length symbol] or 15) + the length's extra bits +
+// (dlen[distance symbol] or 15) + the distance's extra bits.  The walk's kept match -- the longest, the first found among
+// equals, the same three ends, `nice` and the cap -- is a found match iff the sum of lit over its `best` bytes at
+// p .. p + best - 1 is strictly more than match(best, bestd); lit16 is not consulted.  A match costs at most 15 + 5 +
+// 15 + 13 = 48 bits and a literal at least 1, so the sum stops once it is over 48 (at most 49 bytes, all below p + best
+// <= m) without changing the answer.  Links, the lazy step, the greedy resolution and history positions that enter but
+// never search are the same code as in pass 1.
+//   No LDS is added: llen and dlen stay where they are until the next build_code overwrites them, which is after the
+// pass that read them; lcode and dcode are written between passes and read only after the last.  No store to global
+// memory is added beyond the token scratch the tile owns already (at most one token a tile byte, in every pass);
+// FC2_DEFLATE_TILE_BOUND is unchanged.
+//   Bounds (link[]) in a pass that runs again.  link[] is not cleared between passes and does not need to be: the
+// argument above holds per pass once the heads are zero.  With empty heads a pass reads as a first candidate only a
+// head an earlier step of this pass entered, and every further candidate is c - link[c & 32767] with c a position
+// walked in this pass; every position of this pass that can be a head or be reached from one wrote its entry in this
+// pass where it entered itself, before any later step reads it.  So every entry read was written in this pass, and an
+// entry left by the pass before is either overwritten (positions enter in the same order, at the same slots, in every
+// pass: the same p & 32767 for the same p) or never read.  In a region over 32768 bytes, where slots are reused inside
+// one pass, the stale-slot stop is what it was: the slot of c holds c's entry of this pass unless c + 32768 has entered,
+// and the walk ends before reading it where c + 32768 < base + 64.  The falling candidate (c < p, back <= c checked
+// before the subtraction) bounds every load as above: link[] at c & 32767 < min(region rounded up to 4, 32768), region
+// bytes up to c + 258 + 3 < m + 16.  (tests/test_gpu_deflate_priced.py runs deflate_deep_inputs.stale_chain in a region
+// of 65536 bytes with two passes.)
+//   Instantiations.  The nine kernels above are the same template with kPriced = false: the pass loop is a do-while
+// whose condition is the template parameter, and nothing in it is instantiated for them.  Compared in the compiler's
+// output against the parent's: the same instructions in each of the nine (11849 .. 12125 of them), in the same order
+// but for one to three neighbouring register moves (v_mov_b32 0, s_mov_b64 0, one v_cndmask_b32) that the scheduler
+// places one or two slots earlier or later in <2, false>, <2, true, true>, <2, true, true, true> and <2, false, false,
+// true>; the other five are identical line for line (symbol names apart).  Same registers as reported above.  Resource
+// report for gfx950 as above:
+//   <2, false, false, true, true> 70, 104, 0    <2, true, false, true, true> 70, 104, 0    <2, true, true, true, true> 70, 104, 0
+// (one workgroup a CU by its LDS at every tile over some 19 KiB, as level 2: the registers do not limit it).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -385,7 +430,10 @@ __device__ __forceinline__ void put(Lds &L, Out &o, uint32_t v, uint32_t nb) {
 // without it `group` is not looked at.
 // kDeep (level 2 only): the walk's two limits are kernel arguments, `search` = depth | nice << 16 (the header's
 // "Search effort"); without it `search` is not looked at and the limits are kDepth and kNice.
-template <int kLevel, bool kHist, bool kGroups = false, bool kDeep = false>
+// kPriced (with kDeep): `search` carries a number of passes too, depth | nice << 16 | passes << 28, and every pass after
+// the first takes a match by its price in the code the pass before gave (the header's "Priced passes"); without it
+// there is one pass and those bits are not looked at.
+template <int kLevel, bool kHist, bool kGroups = false, bool kDeep = false, bool kPriced = false>
 __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__ src, uint64_t n_bytes, uint32_t tile,
                                                      uint8_t *__restrict__ dst, uint32_t stride,
                                                      uint32_t *__restrict__ out_len, uint32_t *__restrict__ crc,
@@ -393,6 +441,7 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
                                                      uint32_t search) {
     static_assert(kHist || !kGroups, "groups are built on the history's kernel");
     static_assert(kLevel == 2 || !kDeep, "the search effort is level 2's");
+    static_assert(kDeep || !kPriced, "priced passes are built on the search effort's kernel");
     extern __shared__ __align__(16) uint8_t smem[];
     Lds &L = *reinterpret_cast<Lds *>(smem);
     uint32_t *T = L.tile;
@@ -505,124 +554,169 @@ __global__ __launch_bounds__(64) void deflate_kernel(const uint8_t *__restrict__
     // ---- pass 1: matches, tokens, histograms ------------------------------------------------------
     uint32_t ntok = 0, skip = h;                // tokens so far; positions below `skip` are inside a match, or history
     uint32_t extra = 0;                         // this lane's tokens' extra bits
-    for (uint32_t base = 0; base < m; base += 64) {
-        const uint32_t p = base + (uint32_t)lane;
-        const bool can = p + kMinMatch <= m;
-        const uint32_t v = load32u(T, p < m ? p : 0u);
-        const uint32_t h = (v * 2654435761u) >> (32 - kHashBits);
-        const uint32_t cand = can ? L.htab[h] : 0u;
-        __syncthreads();
-        if (can) atomicMax(&L.htab[h], p + 1u);
-        if constexpr (kLevel == 2) {
-            if (can) link[p & (kLinks - 1u)] = (uint16_t)(cand && p + 1u - cand <= kMaxDist ? p + 1u - cand : 0u);
-        }
-        __syncthreads();
-        if (skip >= base + 64u) continue;       // (uniform) the whole step lies inside a match
-        uint32_t mlen = 0, mdist = 0;
-        if constexpr (kLevel == 2) {
-            if (cand && p >= skip) {
-                const uint32_t maxlen = m - p < kMaxMatch ? m - p : kMaxMatch;
-                uint32_t c = cand - 1u, best = 0, bestd = 0;
-                // (kDeep: wave-uniform limits from the kernel argument, in place of the constants)
-                for (int k = 0; k < (kDeep ? (int)(search & 0xFFFFu) : kDepth); ++k) {
-                    const uint32_t d = p - c;
-                    if (d > kMaxDist || c + kLinks < base + 64u) break;
-                    if (load32u(T, c) == v) {
-                        uint32_t l = 4;
-                        while (l < maxlen) {
-                            const uint32_t x = load32u(T, c + l) ^ load32u(T, p + l);
-                            if (x) {
-                                l += (uint32_t)(__ffs((int)x) - 1) >> 3;
-                                break;
+    uint32_t pass = 1;                          // (kPriced: the pass running, wave-uniform)
+    do {
+        for (uint32_t base = 0; base < m; base += 64) {
+            const uint32_t p = base + (uint32_t)lane;
+            const bool can = p + kMinMatch <= m;
+            const uint32_t v = load32u(T, p < m ? p : 0u);
+            const uint32_t h = (v * 2654435761u) >> (32 - kHashBits);
+            const uint32_t cand = can ? L.htab[h] : 0u;
+            __syncthreads();
+            if (can) atomicMax(&L.htab[h], p + 1u);
+            if constexpr (kLevel == 2) {
+                if (can) link[p & (kLinks - 1u)] = (uint16_t)(cand && p + 1u - cand <= kMaxDist ? p + 1u - cand : 0u);
+            }
+            __syncthreads();
+            if (skip >= base + 64u) continue;       // (uniform) the whole step lies inside a match
+            uint32_t mlen = 0, mdist = 0;
+            if constexpr (kLevel == 2) {
+                if (cand && p >= skip) {
+                    const uint32_t maxlen = m - p < kMaxMatch ? m - p : kMaxMatch;
+                    uint32_t c = cand - 1u, best = 0, bestd = 0;
+                    // (kDeep: wave-uniform limits from the kernel argument, in place of the constants)
+                    for (int k = 0; k < (kDeep ? (int)(search & 0xFFFFu) : kDepth); ++k) {
+                        const uint32_t d = p - c;
+                        if (d > kMaxDist || c + kLinks < base + 64u) break;
+                        if (load32u(T, c) == v) {
+                            uint32_t l = 4;
+                            while (l < maxlen) {
+                                const uint32_t x = load32u(T, c + l) ^ load32u(T, p + l);
+                                if (x) {
+                                    l += (uint32_t)(__ffs((int)x) - 1) >> 3;
+                                    break;
+                                }
+                                l += 4;
                             }
-                            l += 4;
+                            l = l < maxlen ? l : maxlen;
+                            if (l > best) {
+                                best = l;
+                                bestd = d;
+                            }
+                            if (best >= (kPriced ? (search >> 16) & 0x1FFu : kDeep ? search >> 16 : kNice) || best >= maxlen) break;
                         }
-                        l = l < maxlen ? l : maxlen;
-                        if (l > best) {
-                            best = l;
-                            bestd = d;
+                        const uint32_t back = link[c & (kLinks - 1u)];
+                        if (!back || back > c) break;   // (back <= c: it points at a position of the tile)
+                        c -= back;
+                    }
+                    bool priced = false;
+                    if constexpr (kPriced) priced = pass > 1u;
+                    if (priced) {
+                        // the match's bits in the last pass's code against its bytes' as literals; a symbol without
+                        // a codeword counts 15.  A match costs 48 bits at most and a literal one at least, so the sum
+                        // stops once it is over 48: at most 49 bytes are read, all below p + best <= m.
+                        if (best) {
+                            uint32_t s, eb, ev;
+                            len_sym(best - 3u, s, eb, ev);
+                            uint32_t price = (L.llen[s] ? L.llen[s] : 15u) + eb;
+                            dist_sym(bestd - 1u, s, eb, ev);
+                            price += (L.dlen[s] ? L.dlen[s] : 15u) + eb;
+                            uint32_t lits = 0;
+                            for (uint32_t i = 0; i < best && lits <= 48u; ++i) {
+                                const uint32_t b = (T[(p + i) >> 2] >> (8u * ((p + i) & 3u))) & 255u;
+                                lits += L.llen[b] ? L.llen[b] : 15u;
+                            }
+                            if (lits > price) {
+                                mlen = best;
+                                mdist = bestd;
+                            }
                         }
-                        if (best >= (kDeep ? search >> 16 : kNice) || best >= maxlen) break;
-                    }
-                    const uint32_t back = link[c & (kLinks - 1u)];
-                    if (!back || back > c) break;   // (back <= c: it points at a position of the tile)
-                    c -= back;
-                }
-                if (best) {
-                    const uint32_t deb = bestd > 4u ? 30u - (uint32_t)__clz((int)(bestd - 1u)) : 0u;
-                    if (best * lit16 >= 16u * (11u + deb)) {
-                        mlen = best;
-                        mdist = bestd;
+                    } else if (best) {
+                        const uint32_t deb = bestd > 4u ? 30u - (uint32_t)__clz((int)(bestd - 1u)) : 0u;
+                        if (best * lit16 >= 16u * (11u + deb)) {
+                            mlen = best;
+                            mdist = bestd;
+                        }
                     }
                 }
-            }
-        } else if (cand && p >= skip) {
-            const uint32_t c = cand - 1u;       // < p: positions of earlier steps only
-            const uint32_t d = p - c;
-            if (d <= kMaxDist && load32u(T, c) == v) {
-                const uint32_t maxlen = m - p < kMaxMatch ? m - p : kMaxMatch;
-                uint32_t l = 4;
-                while (l < maxlen) {
-                    const uint32_t x = load32u(T, c + l) ^ load32u(T, p + l);
-                    if (x) {
-                        l += (uint32_t)(__ffs((int)x) - 1) >> 3;
-                        break;
+            } else if (cand && p >= skip) {
+                const uint32_t c = cand - 1u;       // < p: positions of earlier steps only
+                const uint32_t d = p - c;
+                if (d <= kMaxDist && load32u(T, c) == v) {
+                    const uint32_t maxlen = m - p < kMaxMatch ? m - p : kMaxMatch;
+                    uint32_t l = 4;
+                    while (l < maxlen) {
+                        const uint32_t x = load32u(T, c + l) ^ load32u(T, p + l);
+                        if (x) {
+                            l += (uint32_t)(__ffs((int)x) - 1) >> 3;
+                            break;
+                        }
+                        l += 4;
                     }
-                    l += 4;
-                }
-                l = l < maxlen ? l : maxlen;
-                // worth it if the length and distance codes (about 11 bits and the distance's extra
-                // bits) cost less than the bytes as literals
-                const uint32_t deb = d > 4u ? 30u - (uint32_t)__clz((int)(d - 1u)) : 0u;
-                if (l >= kMinMatch && l * lit16 >= 16u * (11u + deb)) {
-                    mlen = l;
-                    mdist = d;
-                }
-            }
-        }
-        const uint64_t found = __ballot(mlen != 0);
-        uint64_t starts = 0;                    // lanes whose match is taken
-        uint64_t cov = skip > base ? (1ull << (skip - base)) - 1ull : 0ull;   // lanes inside a match
-        uint32_t cur = skip > base ? skip - base : 0u;                        // < 64
-        while (cur < 64u) {
-            const uint64_t mm = found & ~((1ull << cur) - 1ull);
-            if (!mm) break;
-            const uint32_t l = (uint32_t)__ffsll((long long)mm) - 1u;
-            const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)l);
-            if constexpr (kLevel == 2) {        // a longer match one position on: this one is a literal
-                if (l + 1u < 64u && ((found >> (l + 1u)) & 1ull) &&
-                    (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)((l + 1u) & 63u)) > len) {
-                    cur = l + 1u;
-                    continue;
+                    l = l < maxlen ? l : maxlen;
+                    // worth it if the length and distance codes (about 11 bits and the distance's extra
+                    // bits) cost less than the bytes as literals
+                    const uint32_t deb = d > 4u ? 30u - (uint32_t)__clz((int)(d - 1u)) : 0u;
+                    if (l >= kMinMatch && l * lit16 >= 16u * (11u + deb)) {
+                        mlen = l;
+                        mdist = d;
+                    }
                 }
             }
-            starts |= 1ull << l;
-            const uint32_t e = l + len;         // the first position after the match
-            const uint64_t upto = e >= 64u ? ~0ull : (1ull << e) - 1ull;
-            cov |= upto & ~((2ull << l) - 1ull);
-            cur = e;
-            skip = base + e;
-        }
-        const bool emit = p < m && !((cov >> lane) & 1ull);
-        const uint64_t em = __ballot(emit);
-        if (emit) {
-            const uint32_t at = ntok + (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
-            if ((starts >> lane) & 1ull) {
-                tok[at] = kTokMatch | ((mlen - 3u) << 16) | (mdist - 1u);
-                uint32_t s, eb, ev;
-                len_sym(mlen - 3u, s, eb, ev);
-                atomicAdd(&L.lfreq[s], 1u);
-                extra += eb;
-                dist_sym(mdist - 1u, s, eb, ev);
-                atomicAdd(&L.dfreq[s], 1u);
-                extra += eb;
-            } else {
-                tok[at] = v & 255u;
-                atomicAdd(&L.lfreq[v & 255u], 1u);
+            const uint64_t found = __ballot(mlen != 0);
+            uint64_t starts = 0;                    // lanes whose match is taken
+            uint64_t cov = skip > base ? (1ull << (skip - base)) - 1ull : 0ull;   // lanes inside a match
+            uint32_t cur = skip > base ? skip - base : 0u;                        // < 64
+            while (cur < 64u) {
+                const uint64_t mm = found & ~((1ull << cur) - 1ull);
+                if (!mm) break;
+                const uint32_t l = (uint32_t)__ffsll((long long)mm) - 1u;
+                const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)l);
+                if constexpr (kLevel == 2) {        // a longer match one position on: this one is a literal
+                    if (l + 1u < 64u && ((found >> (l + 1u)) & 1ull) &&
+                        (uint32_t)__builtin_amdgcn_readlane((int)mlen, (int)((l + 1u) & 63u)) > len) {
+                        cur = l + 1u;
+                        continue;
+                    }
+                }
+                starts |= 1ull << l;
+                const uint32_t e = l + len;         // the first position after the match
+                const uint64_t upto = e >= 64u ? ~0ull : (1ull << e) - 1ull;
+                cov |= upto & ~((2ull << l) - 1ull);
+                cur = e;
+                skip = base + e;
             }
+            const bool emit = p < m && !((cov >> lane) & 1ull);
+            const uint64_t em = __ballot(emit);
+            if (emit) {
+                const uint32_t at = ntok + (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
+                if ((starts >> lane) & 1ull) {
+                    tok[at] = kTokMatch | ((mlen - 3u) << 16) | (mdist - 1u);
+                    uint32_t s, eb, ev;
+                    len_sym(mlen - 3u, s, eb, ev);
+                    atomicAdd(&L.lfreq[s], 1u);
+                    extra += eb;
+                    dist_sym(mdist - 1u, s, eb, ev);
+                    atomicAdd(&L.dfreq[s], 1u);
+                    extra += eb;
+                } else {
+                    tok[at] = v & 255u;
+                    atomicAdd(&L.lfreq[v & 255u], 1u);
+                }
+            }
+            ntok += (uint32_t)__popcll(em);
         }
-        ntok += (uint32_t)__popcll(em);
-    }
+        if constexpr (kPriced) {
+            // a pass that is not the last: the two codes of its histograms, built as after the last one; then the heads
+            // (the code builder worked in them) and the histograms are zeroed and pass 1 runs again over the same
+            // region, writing its tokens over the scratch.  llen and dlen stay until the next build_code, after the
+            // pass that reads them.  A code that is not ok (not expected) ends the passes: the tile goes on below.
+            if (pass >= search >> 28) break;
+            if (lane == 0) L.lfreq[256] = 1;
+            Work &W = *reinterpret_cast<Work *>(L.htab);
+            bool again = build_code(L.lfreq, 286, 15, L.llen, L.lcode, L.blc, W, lane);
+            again = build_code(L.dfreq, 30, 15, L.dlen, L.dcode, L.blc, W, lane) && again;
+            if (!again) break;
+            for (uint32_t k = (uint32_t)lane; k < (1u << kHashBits); k += 64) L.htab[k] = 0;
+            for (uint32_t k = (uint32_t)lane; k < 288u; k += 64) L.lfreq[k] = 0;
+            if (lane < 32) L.dfreq[lane] = 0;
+            ntok = 0;
+            skip = h;
+            extra = 0;
+            ++pass;
+            __syncthreads();
+        }
+    } while (kPriced);
     for (int s = 1; s < 64; s <<= 1) extra += (uint32_t)__shfl_xor((int)extra, s);
     extra = uni(extra);
     if (lane == 0) L.lfreq[256] = 1;            // the end of the block
@@ -798,7 +892,7 @@ uint64_t group_tiles(uint64_t n_bytes, uint32_t group, uint32_t tile) {
     return n_bytes / group * tpg + (rest + tile - 1) / tile;
 }
 
-template <int kLevel, bool kHist, bool kGroups = false, bool kDeep = false>
+template <int kLevel, bool kHist, bool kGroups = false, bool kDeep = false, bool kPriced = false>
 int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, uint8_t *dst, uint32_t stride, uint32_t *out_len,
            uint32_t *crc, void *scratch, void *stream, uint32_t group = 0, uint32_t search = 0) {
     if (!tile || tile > kTileMax) return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch: tile must be 1..65536");
@@ -815,12 +909,12 @@ int launch(const uint8_t *src, uint64_t n_bytes, uint32_t tile, uint32_t hist, u
     if (hipGetDevice(&dev) != hipSuccess) return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: no current device");
     const uint64_t bit = 1ull << (dev & 63);
     if (!(reserved.load() & bit)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel<kLevel, kHist, kGroups, kDeep>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_kernel<kLevel, kHist, kGroups, kDeep, kPriced>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kTileMax, kLevel)) != hipSuccess)
             return fc2::fail(FC2_E_HIP, "fc2_deflate_launch: cannot reserve the kernel's LDS");
         reserved |= bit;
     }
-    hipLaunchKernelGGL((deflate_kernel<kLevel, kHist, kGroups, kDeep>), dim3((uint32_t)tiles), dim3(64), lds_bytes(tile + hist, kLevel),
+    hipLaunchKernelGGL((deflate_kernel<kLevel, kHist, kGroups, kDeep, kPriced>), dim3((uint32_t)tiles), dim3(64), lds_bytes(tile + hist, kLevel),
                        (hipStream_t)stream, src, n_bytes, tile, dst, stride, out_len, crc, static_cast<uint32_t *>(scratch),
                        hist, group, search);
     const hipError_t e = hipGetLastError();
@@ -886,4 +980,23 @@ extern "C" int fc2_deflate_launch_deep(const uint8_t *src, uint64_t n_bytes, uin
     if (group) return launch<2, true, true, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, group, search);
     if (hist) return launch<2, true, false, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, 0, search);
     return launch<2, false, false, true>(src, n_bytes, tile, 0, dst, stride, out_len, crc, scratch, stream, 0, search);
+}
+
+extern "C" int fc2_deflate_launch_priced(const uint8_t *src, uint64_t n_bytes, uint32_t group, uint32_t tile, uint32_t hist,
+                                         uint8_t *dst, uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch,
+                                         void *stream, uint32_t depth, uint32_t nice, uint32_t passes) {
+    if (passes < FC2_DEFLATE_PASSES_MIN || passes > FC2_DEFLATE_PASSES_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_priced: passes is 1..3");
+    if (depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX || nice < FC2_DEFLATE_NICE_MIN ||
+        nice > FC2_DEFLATE_NICE_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_priced: depth is 1..128, nice 4..258");
+    if (!tile || tile > kTileMax || hist > kMaxDist || tile + hist > kTileMax)
+        return fc2::fail(FC2_E_PARAM, "fc2_deflate_launch_priced: tile must be 1..65536, hist 0..32768, tile + hist <= 65536");
+    if (passes == 1)
+        return fc2_deflate_launch_deep(src, n_bytes, group, tile, hist, dst, stride, out_len, crc, scratch, stream, depth, nice);
+    const uint32_t search = depth | (nice << 16) | (passes << 28);
+    if (group)
+        return launch<2, true, true, true, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, group, search);
+    if (hist) return launch<2, true, false, true, true>(src, n_bytes, tile, hist, dst, stride, out_len, crc, scratch, stream, 0, search);
+    return launch<2, false, false, true, true>(src, n_bytes, tile, 0, dst, stride, out_len, crc, scratch, stream, 0, search);
 }

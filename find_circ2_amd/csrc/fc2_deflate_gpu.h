@@ -27,9 +27,10 @@ constexpr double kDefaultTimeout = 60.0;       // seconds a wait for the device 
 // is one launch of fc2_deflate_launch_hist -- every tile but the piece's first has the `hist` bytes before it as
 // its window -- and becomes one gzip member (fc2_gzmember_impl.h) instead of one per tile; pieces stay
 // independent of each other.  depth, nice (both 0: the level's own search): level 2's search effort,
-// fc2_deflate_launch_deep's depth 1..128 and nice 4..258 -- refused unless level is 2
+// fc2_deflate_launch_deep's depth 1..128 and nice 4..258 -- refused unless level is 2.  passes (0: one):
+// fc2_deflate_launch_priced's 1..3, with that search effort or level 2's own -- refused unless level is 2
 Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err,
-              uint32_t depth = 0, uint32_t nice = 0);
+              uint32_t depth = 0, uint32_t nice = 0, uint32_t passes = 0);
 // frees everything; a device that timed out is not waited for (its buffers are left to the process's end)
 void gpu_close(Gpu *g);
 size_t gpu_max_piece(const Gpu *g);

@@ -43,6 +43,7 @@ struct Gpu {
     int level = 1;
     uint32_t hist = 0;                         // > 0: fc2_deflate_launch_hist, and a piece is one member
     uint32_t depth = 0, nice = 0;              // depth > 0: fc2_deflate_launch_deep with these (level 2 only)
+    uint32_t passes = 0;                       // > 1: fc2_deflate_launch_priced with these (level 2 only)
     bool hung = false;                         // a wait timed out: the device is not touched again
     Slot slot[kSlots];
 };
@@ -54,7 +55,7 @@ static bool hip_ok(hipError_t e, const char *what, std::string &err) {
 }
 
 Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err,
-              uint32_t depth, uint32_t nice) {
+              uint32_t depth, uint32_t nice, uint32_t passes) {
     if (!tile || tile > 65536 || !max_piece || device < 0 || level < 1 || level > 2 || hist > 32768 || tile + hist > 65536) {
         err = "GPU gzip: bad tile, history, piece size, device or level";
         return nullptr;
@@ -62,6 +63,10 @@ Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int
     if ((depth || nice) && (level != 2 || depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX ||
                             nice < FC2_DEFLATE_NICE_MIN || nice > FC2_DEFLATE_NICE_MAX)) {
         err = "GPU gzip: the search effort needs level 2, depth 1..128 and nice 4..258";
+        return nullptr;
+    }
+    if (passes && (level != 2 || passes < FC2_DEFLATE_PASSES_MIN || passes > FC2_DEFLATE_PASSES_MAX)) {
+        err = "GPU gzip: passes need level 2 and are 1..3";
         return nullptr;
     }
     Gpu *g = new Gpu();
@@ -74,6 +79,7 @@ Gpu *gpu_open(int device, size_t max_piece, uint32_t tile, double timeout_s, int
     g->hist = hist;
     g->depth = depth;
     g->nice = nice;
+    g->passes = passes;
     g->max_tiles = (uint32_t)((max_piece + tile - 1) / tile);
     const size_t dst = (size_t)g->max_tiles * g->stride, meta = (size_t)g->max_tiles * 2 * sizeof(uint32_t);
     bool ok = hip_ok(hipSetDevice(device), "hipSetDevice", err);
@@ -140,7 +146,11 @@ bool gpu_submit(Gpu *g, int k, const char *data, size_t n, std::string &err) {
     s.busy = true;
     const bool ok =
         hip_ok(hipMemcpyAsync(s.d_src, s.h_src, n, hipMemcpyHostToDevice, s.stream), "upload", err) &&
-        ((g->depth ? fc2_deflate_launch_deep(s.d_src, n, 0, g->tile, g->hist, s.d_dst, g->stride, s.d_meta,
+        ((g->passes > 1
+              ? fc2_deflate_launch_priced(s.d_src, n, 0, g->tile, g->hist, s.d_dst, g->stride, s.d_meta, s.d_meta + g->max_tiles,
+                                          s.d_scratch, s.stream, g->depth ? g->depth : FC2_DEFLATE_LEVEL2_DEPTH,
+                                          g->depth ? g->nice : FC2_DEFLATE_LEVEL2_NICE, g->passes)
+          : g->depth ? fc2_deflate_launch_deep(s.d_src, n, 0, g->tile, g->hist, s.d_dst, g->stride, s.d_meta,
                                              s.d_meta + g->max_tiles, s.d_scratch, s.stream, g->depth, g->nice)
                    : fc2_deflate_launch_hist(s.d_src, n, g->tile, g->hist, s.d_dst, g->stride, s.d_meta,
                                              s.d_meta + g->max_tiles, s.d_scratch, s.stream, g->level)) == FC2_OK ||
@@ -251,7 +261,7 @@ extern "C" int fc2_gpu_gzip_level(int device, const void *in, uint64_t n, uint32
 
 namespace {
 int gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, int level, uint32_t depth, uint32_t nice,
-             void *out, uint64_t cap, uint64_t *out_n);
+             void *out, uint64_t cap, uint64_t *out_n, uint32_t passes = 0);
 }  // namespace
 
 extern "C" int fc2_gpu_gzip_hist(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, int level, void *out,
@@ -267,9 +277,19 @@ extern "C" int fc2_gpu_gzip_deep(int device, const void *in, uint64_t n, uint32_
     return gpu_gzip(device, in, n, tile, hist, 2, depth, nice, out, cap, out_n);
 }
 
+extern "C" int fc2_gpu_gzip_priced(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, uint32_t depth,
+                                   uint32_t nice, uint32_t passes, void *out, uint64_t cap, uint64_t *out_n) {
+    if (passes < FC2_DEFLATE_PASSES_MIN || passes > FC2_DEFLATE_PASSES_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_gpu_gzip_priced: passes is 1..3");
+    if (depth < FC2_DEFLATE_DEPTH_MIN || depth > FC2_DEFLATE_DEPTH_MAX || nice < FC2_DEFLATE_NICE_MIN ||
+        nice > FC2_DEFLATE_NICE_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_gpu_gzip_priced: depth is 1..128, nice 4..258");
+    return gpu_gzip(device, in, n, tile, hist, 2, depth, nice, out, cap, out_n, passes);
+}
+
 namespace {
 int gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, int level, uint32_t depth, uint32_t nice,
-             void *out, uint64_t cap, uint64_t *out_n) {
+             void *out, uint64_t cap, uint64_t *out_n, uint32_t passes) {
     using namespace fc2;
     if (!tile || tile > 65536 || device < 0 || !out || !out_n || (!in && n) || level < 1 || level > 2 || hist > 32768 ||
         tile + hist > 65536)
@@ -287,7 +307,7 @@ int gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, uint32_t his
     }
     const size_t piece = size_t(4) << 20;
     std::string err;
-    dgz::Gpu *g = dgz::gpu_open(device, piece, tile, 0, level, hist, err, depth, nice);
+    dgz::Gpu *g = dgz::gpu_open(device, piece, tile, 0, level, hist, err, depth, nice, passes);
     if (!g) return fc2::fail(FC2_E_HIP, "fc2_gpu_gzip: " + err);
     const char *src = static_cast<const char *>(in);
     const uint64_t pieces = (n + piece - 1) / piece;

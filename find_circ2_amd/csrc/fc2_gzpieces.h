@@ -52,11 +52,11 @@ class GzPieces {
     // at most timeout_s seconds for the device, at the compressor's `level`, every tile with the `hist` bytes of
     // its piece before it as its window (0: none) (call right after open()); false and err if tile + hist is
     // over 65536 or the device's buffers cannot be made (the file then stays on the CPU); depth, nice: level 2's
-    // search effort (dgz::gpu_open; 0, 0: the level's own)
+    // search effort (dgz::gpu_open; 0, 0: the level's own); passes: level 2's passes (dgz::gpu_open; 0: one)
     bool set_device(int device, uint32_t tile, double timeout_s, int level, uint32_t hist, std::string &err, uint32_t depth = 0,
-                    uint32_t nice = 0) {
+                    uint32_t nice = 0, uint32_t passes = 0) {
         if (!f_ || gpu_ || wrote_any_) { err = "GPU gzip: set the device once, after open and before any text"; return false; }
-        gpu_ = dgz::gpu_open(device, 2 * piece_, tile ? tile : dgz::kDefaultTile, timeout_s, level, hist, err, depth, nice);   // (append_owned: up to two pieces long)
+        gpu_ = dgz::gpu_open(device, 2 * piece_, tile ? tile : dgz::kDefaultTile, timeout_s, level, hist, err, depth, nice, passes);   // (append_owned: up to two pieces long)
         device_mode_ = gpu_ != nullptr;
         return device_mode_;
     }

@@ -31,6 +31,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../include/fc2_caller.h"
 #include "../../include/fc2_ingest.h"
 #include "fc2_bam_frag_impl.h"
 #include "fc2_bamout.h"
@@ -644,6 +645,7 @@ struct fc2_ingest {
     int bam_level = 1;                          // fc2_ingest_set_bam_out_device_level
     uint32_t bam_tile = 0, bam_hist = 0;        // fc2_ingest_set_bam_out_device_tiles
     uint32_t bam_depth = 0, bam_nice = 0;       // fc2_ingest_set_bam_out_device_search (0, 0: the level's own)
+    uint32_t bam_passes = 0;                    // fc2_ingest_set_bam_out_device_passes (0: one)
     // grouping state
     bool started = false;
     Mate current, other;
@@ -2409,9 +2411,11 @@ extern "C" int fc2_ingest_set_bam_out_device(fc2_ingest *h, int mode, int device
                                       "65536 bytes together");
     if (mode && h->bam_depth && h->bam_level != 2)
         return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: the search effort needs level 2");
+    if (mode && h->bam_passes && h->bam_level != 2)
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device: the passes need level 2");
     std::string err;
     if (!fc2::bam::set_device(h->bam_out, mode, device, block, piece_blocks, timeout_s, h->bam_level, h->bam_tile,
-                              h->bam_hist, err, h->bam_depth, h->bam_nice))
+                              h->bam_hist, err, h->bam_depth, h->bam_nice, h->bam_passes))
         return fc2::fail(mode == 1 ? FC2_E_HIP : FC2_E_PARAM, "fc2_ingest_set_bam_out_device: " + err);
     return FC2_OK;
 }
@@ -2450,6 +2454,20 @@ extern "C" int fc2_ingest_set_bam_out_device_search(fc2_ingest *h, uint32_t dept
                                       "(fc2_ingest_set_bam_out_device_level)");
     h->bam_depth = depth;
     h->bam_nice = nice;
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_set_bam_out_device_passes(fc2_ingest *h, uint32_t passes) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_passes: null argument");
+    if (!h->bam_out || h->n_records || fc2::bam::device_set(h->bam_out))
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_passes: call after fc2_ingest_set_bam_out, before "
+                                      "fc2_ingest_set_bam_out_device and before reading");
+    if (passes < FC2_DEFLATE_PASSES_MIN || passes > FC2_DEFLATE_PASSES_MAX)
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_passes: passes is 1..3");
+    if (h->bam_level != 2)
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_device_passes: set level 2 first "
+                                      "(fc2_ingest_set_bam_out_device_level)");
+    h->bam_passes = passes;
     return FC2_OK;
 }
 

@@ -148,6 +148,8 @@ def set_bam_out_device(h, bam_device) -> None:
         N.check(N.lib().fc2_ingest_set_bam_out_device_level(h, int(d["level"])))
     if d.get("depth") is not None or d.get("nice") is not None:     # level 2's search effort (else its own 8 and 32)
         N.check(N.lib().fc2_ingest_set_bam_out_device_search(h, _u32(d.get("depth"), 8), _u32(d.get("nice"), 32)))
+    if d.get("passes") is not None:                                 # level 2's passes (else one)
+        N.check(N.lib().fc2_ingest_set_bam_out_device_passes(h, _u32(d["passes"], 1)))
     if int(d.get("tile", 0)) or int(d.get("hist", 0)):
         N.check(N.lib().fc2_ingest_set_bam_out_device_tiles(h, int(d.get("tile", 0)), int(d.get("hist", 0))))
     N.check(N.lib().fc2_ingest_set_bam_out_device(h, int(d.get("mode", 1)), int(d.get("device", 0)), int(d.get("block", 0)),

@@ -75,7 +75,7 @@ class NativeCaller:
                  bam_out: str = "", reads_gz=None, inflate_device=None, inflate_after: int = 0,
                  gzip_device=None, gzip_tile: int = 0, gzip_timeout_s: float = 0.0, gpu_walk: bool = True,
                  gpu_digest: bool = False, gpu_group: int = 0, bam_device=None, gzip_level: int = 1,
-                 gzip_history: int = 0, gzip_search=None):
+                 gzip_history: int = 0, gzip_search=None, gzip_passes=None):
         o = copts
         # the strings must outlive the handle's open call (fc2_caller_open copies them)
         self._keep = [o.name.encode(), known_circ.encode() if known_circ else None,
@@ -107,6 +107,7 @@ class NativeCaller:
         self.gzip_level = int(gzip_level)      # ... at this level of the GPU compressor (1 or 2)
         self.gzip_history = int(gzip_history)  # ... a tile referring to this many bytes before it (0: none; a piece is then one member)
         self.gzip_search = gzip_search         # ... level 2 searching with this (depth, nice) (None: its own 8 and 32)
+        self.gzip_passes = gzip_passes         # ... level 2 parsing every tile this many times (None: once)
         self.opened = False
         self.format = None           # "sam" | "bam", detected from the bytes (open)
         self.loop_profile = {}       # seconds per stage of the last run (two-thread loop)
@@ -143,6 +144,9 @@ class NativeCaller:
                     from .ingest import _u32
                     depth, nice = self.gzip_search
                     N.check(L.fc2_caller_set_reads_gz_device_search(self.h, _u32(depth, 8), _u32(nice, 32)))
+                if self.gzip_passes is not None:
+                    from .ingest import _u32
+                    N.check(L.fc2_caller_set_reads_gz_device_passes(self.h, _u32(self.gzip_passes, 1)))
                 if self.gzip_history:
                     N.check(L.fc2_caller_set_reads_gz_device_history(self.h, self.gzip_history))
                 N.check(L.fc2_caller_set_reads_gz_device(self.h, int(self.gzip_device)))

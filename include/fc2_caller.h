@@ -145,6 +145,12 @@ int fc2_caller_set_reads_gz_device_history(fc2_caller *h, uint32_t hist);
  * fc2_caller_set_reads_gz_device itself is refused (FC2_E_PARAM).  The command line passes FC2_GPU_GZIP_DEPTH and
  * FC2_GPU_GZIP_NICE here. */
 int fc2_caller_set_reads_gz_device_search(fc2_caller *h, uint32_t depth, uint32_t nice);
+/* This handle's passes at level 2 on the device (fc2_deflate_launch_priced's 1..3; not called: 1), beside whatever
+ * search effort is set, for the device mode set afterwards with fc2_caller_set_reads_gz_device.  Refused exactly as
+ * fc2_caller_set_reads_gz_device_search is: FC2_E_PARAM while the level is 1, for a value out of range and for a
+ * call after fc2_caller_set_reads_gz_device; and fc2_caller_set_reads_gz_device itself is refused if the level is
+ * set back to 1 afterwards.  The command line passes FC2_GPU_GZIP_PASSES here. */
+int fc2_caller_set_reads_gz_device_passes(fc2_caller *h, uint32_t passes);
 /* pieces the device compressed, and pieces of the device mode the CPU compressed, so far (0, 0 without it) */
 int fc2_caller_reads_gz_counts(const fc2_caller *h, uint64_t *gpu_pieces, uint64_t *cpu_pieces);
 
@@ -202,6 +208,23 @@ uint64_t fc2_deflate_group_tiles(uint64_t n_bytes, uint32_t group, uint32_t tile
 int fc2_deflate_launch_deep(const uint8_t *src, uint64_t n_bytes, uint32_t group, uint32_t tile, uint32_t hist,
                             uint8_t *dst, uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch,
                             void *stream, uint32_t depth, uint32_t nice);
+/* the range of fc2_deflate_launch_priced's passes */
+#define FC2_DEFLATE_PASSES_MIN 1u
+#define FC2_DEFLATE_PASSES_MAX 3u
+/* level 2's own search effort: what the passes run with where no other is set */
+#define FC2_DEFLATE_LEVEL2_DEPTH 8u
+#define FC2_DEFLATE_LEVEL2_NICE 32u
+/* fc2_deflate_launch_deep with `passes` parses of every tile.  The first is fc2_deflate_launch_deep's; after a pass
+ * that is not the last the literal/length and distance codes are built from its histograms, and the next pass runs
+ * the same search from the tile's (or its history's) start with one difference: the walk's kept match is taken only
+ * if its bytes, as literals in that code, cost strictly more bits than its length and distance codewords and their
+ * extra bits (a symbol without a codeword counts 15).  The last pass's tokens are written; the stored form still
+ * bounds a tile.  passes = 1 is fc2_deflate_launch_deep byte for byte.  Same shapes, slots, scratch and bound.
+ * passes outside 1..3 is FC2_E_PARAM before the device is touched, as is everything fc2_deflate_launch_deep
+ * refuses.  tests/deflate_model_priced.py is the rule in Python. */
+int fc2_deflate_launch_priced(const uint8_t *src, uint64_t n_bytes, uint32_t group, uint32_t tile, uint32_t hist,
+                              uint8_t *dst, uint32_t stride, uint32_t *out_len, uint32_t *crc, void *scratch,
+                              void *stream, uint32_t depth, uint32_t nice, uint32_t passes);
 /* one buffer through the host path of spliced_reads.fastq.gz's device mode, for tests and other hosts: gzip
  * members (one per tile) of in[0, n) into out (cap bytes); FC2_E_RANGE if they do not fit. */
 int fc2_gpu_gzip(int device, const void *in, uint64_t n, uint32_t tile, void *out, uint64_t cap, uint64_t *out_n);
@@ -217,6 +240,10 @@ int fc2_gpu_gzip_hist(int device, const void *in, uint64_t n, uint32_t tile, uin
  * fc2_gpu_gzip_bound holds. */
 int fc2_gpu_gzip_deep(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, uint32_t depth, uint32_t nice,
                       void *out, uint64_t cap, uint64_t *out_n);
+/* fc2_gpu_gzip_deep with fc2_deflate_launch_priced's passes (1..3, else FC2_E_PARAM before the device is touched);
+ * passes = 1: fc2_gpu_gzip_deep's bytes.  fc2_gpu_gzip_bound holds. */
+int fc2_gpu_gzip_priced(int device, const void *in, uint64_t n, uint32_t tile, uint32_t hist, uint32_t depth, uint32_t nice,
+                        uint32_t passes, void *out, uint64_t cap, uint64_t *out_n);
 uint64_t fc2_gpu_gzip_bound(uint64_t n, uint32_t tile);
 
 /* ---- BGZF output on the GPU (csrc/fc2_bgzf_out.hip; the rule: csrc/fc2_bgzf_frame_impl.h) ---- */
@@ -254,6 +281,11 @@ int fc2_gpu_bgzf_tiles(int device, const void *in, uint64_t n, uint32_t block, u
  * values do not depend on the search; fc2_gpu_bgzf_tiles_bound holds. */
 int fc2_gpu_bgzf_deep(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
                       uint32_t hist, uint32_t depth, uint32_t nice, void *out, uint64_t cap, uint64_t *out_n);
+/* fc2_gpu_bgzf_deep with fc2_deflate_launch_priced's passes (1..3, else FC2_E_PARAM before the device is touched);
+ * passes = 1: fc2_gpu_bgzf_deep's bytes.  The ISIZE values do not depend on it; fc2_gpu_bgzf_tiles_bound holds. */
+int fc2_gpu_bgzf_priced(int device, const void *in, uint64_t n, uint32_t block, uint32_t piece_blocks, uint32_t tile,
+                        uint32_t hist, uint32_t depth, uint32_t nice, uint32_t passes, void *out, uint64_t cap,
+                        uint64_t *out_n);
 /* the bytes fc2_gpu_bgzf_tiles needs at most: fc2_gpu_bgzf_bound's with every tile's stream at its worst */
 uint64_t fc2_gpu_bgzf_tiles_bound(uint64_t n, uint32_t block, uint32_t tile);
 uint64_t fc2_gpu_bgzf_bound(uint64_t n, uint32_t block);

@@ -113,6 +113,11 @@ int fc2_ingest_set_bam_out_device_level(fc2_ingest *h, int level);
  * reading has begun.  If the level is set back to 1 afterwards, fc2_ingest_set_bam_out_device itself is refused
  * (FC2_E_PARAM).  The command line passes FC2_GPU_BAM_DEPTH and FC2_GPU_BAM_NICE here. */
 int fc2_ingest_set_bam_out_device_search(fc2_ingest *h, uint32_t depth, uint32_t nice);
+/* The passes mode 1 compresses with at level 2 (fc2_deflate_launch_priced, include/fc2_caller.h: 1..3,
+ * FC2_DEFLATE_PASSES_MIN .. _MAX there; not called: 1), beside whatever search effort is set; mode 2 ignores it.
+ * Called and refused exactly as fc2_ingest_set_bam_out_device_search is.  The command line passes
+ * FC2_GPU_BAM_PASSES here. */
+int fc2_ingest_set_bam_out_device_passes(fc2_ingest *h, uint32_t passes);
 /* Tiles inside a block, for the device mode set afterwards with fc2_ingest_set_bam_out_device: every block of the
  * record bytes is cut into tiles of `tile` bytes, each compressed by a wavefront of its own with the min(hist,
  * its offset in the block) bytes of its block before it as history, and the block's streams, combined CRC-32 and

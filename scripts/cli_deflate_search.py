@@ -1,6 +1,7 @@
 """The command line with -B and both GPU writers at level 2 over a grid of search efforts (FC2_GPU_BAM_DEPTH / _NICE,
 FC2_GPU_GZIP_DEPTH / _NICE; DESIGN.md §5 "Search effort at level 2"), on the inputs of scripts/cli_steady.py.
-Part "sizes": one run per setting, without and with the tiles (FC2_GPU_BAM_TILE, FC2_GPU_BAM_HISTORY,
+A grid entry D:N:P adds FC2_GPU_BAM_PASSES / FC2_GPU_GZIP_PASSES (DESIGN.md §5 "Priced passes at level 2"); :D:N left
+empty (::P) leaves the search at level 2's own.  Part "sizes": one run per setting, without and with the tiles (FC2_GPU_BAM_TILE, FC2_GPU_BAM_HISTORY,
 FC2_GPU_GZIP_HISTORY), each file's size against the CPU writers' of a default run (zlib level 6 for
 spliced_alignments.bam, libdeflate level 1 for spliced_reads.fastq.gz) and the SHA-256 of what each file holds
 against that run's.  Part "loop": --chosen D:N against level 2 alone, interleaved, --reps clean runs each: loop
@@ -48,8 +49,9 @@ def main():
         tiles = {k: v for k, v in tiles.items() if "BAM" in k}
 
     def search(setting):
-        d, n = setting.split(":")
-        both = {"FC2_GPU_BAM_DEPTH": d, "FC2_GPU_BAM_NICE": n, "FC2_GPU_GZIP_DEPTH": d, "FC2_GPU_GZIP_NICE": n}
+        d, n, p = (setting.split(":") + [""])[:3]
+        both = {"FC2_GPU_BAM_DEPTH": d, "FC2_GPU_BAM_NICE": n, "FC2_GPU_GZIP_DEPTH": d, "FC2_GPU_GZIP_NICE": n,
+                "FC2_GPU_BAM_PASSES": p, "FC2_GPU_GZIP_PASSES": p}
         return {k: v for k, v in both.items() if a.writers == "both" or "BAM" in k}
 
     d = tempfile.mkdtemp(prefix="fc2_search_", dir="/tmp")

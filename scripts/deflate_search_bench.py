@@ -3,10 +3,11 @@ level 2 itself in one process: the record bytes of a BAM file (--bam FILE: its i
 in blocks of 0xff00 bytes, untiled and cut into tiles (--tile 16320 --hist 32768), and the text of a gzip file
 (--gz FILE) in tiles of 32768 bytes without and with 32768 bytes of history.  For every shape: level 2 through its
 existing entry (fc2_deflate_launch_level, _groups, _hist), then every (depth, nice) of --grid through
-fc2_deflate_launch_deep.  Timed with HIP events on the launch stream, --reps launches of every piece (the writers'
+fc2_deflate_launch_deep -- or, for an entry depth:nice:passes, through fc2_deflate_launch_priced (csrc/fc2_deflate.hip
+"Priced passes").  Timed with HIP events on the launch stream, --reps launches of every piece (the writers'
 pieces: 64 blocks of records, 4 MiB of text), min and max of a whole pass and per piece; the streams' bytes (for
 records: as BGZF, 26 bytes a block more) against zlib level 6 over the same blocks; every stream inflated by zlib
-and compared; at (8, 32) the slots compared with level 2's.  --lib PATH: the existing entries of another build of
+and compared; at (8, 32) and at 8:32:1 the slots compared with level 2's.  --lib PATH: the existing entries of another build of
 the library (a parent commit's) timed in the same process, first and last, and its slots compared.  One JSON line a
 row.  Measurement infrastructure (not part of the product).
 
@@ -91,7 +92,9 @@ def main():
             x0, k, t0 = starts[p], min(piece, n - starts[p]), first[p]
             args = (slots.data_ptr() + t0 * stride, stride, ln.data_ptr() + 4 * t0, cr.data_ptr() + 4 * t0,
                     scratch.data_ptr() + 4 * x0, sp)
-            if setting is not None:
+            if setting is not None and len(setting) == 3:
+                check(L.fc2_deflate_launch_priced(src.data_ptr() + x0, k, group, tile, hist, *args, *setting))
+            elif setting is not None:
                 check(L.fc2_deflate_launch_deep(src.data_ptr() + x0, k, group, tile, hist, *args, setting[0], setting[1]))
             elif group:
                 check(lib.fc2_deflate_launch_groups(src.data_ptr() + x0, k, group, tile, hist, *args, 2))
@@ -130,7 +133,8 @@ def main():
                 i += cnt
             total = int(lens.astype(np.uint64).sum()) + overhead * len(range(0, n, unit))
             row = {"shape": name, "tag": tag, "depth": setting[0] if setting else 8, "nice": setting[1] if setting else 32,
-                   "entry": "deep" if setting else "level2", "bytes_in": n, "tile": tile, "hist": hist, "group": group,
+                   "passes": setting[2] if setting and len(setting) == 3 else 1,
+                   "entry": ("priced" if len(setting) == 3 else "deep") if setting else "level2", "bytes_in": n, "tile": tile, "hist": hist, "group": group,
                    "pieces": len(starts), "piece_bytes": piece, "bad_streams": int(bad), "bytes_out": total,
                    "zlib6_bytes": z6, "over_zlib6": round(total / z6, 4), "pass_ms_every": passes,
                    "pass_ms_min": min(passes), "pass_ms_max": max(passes),
@@ -151,7 +155,7 @@ def main():
             r, s = run("tree", L, g)
             r["bytes_over_level2"] = round(r["bytes_out"] / rows[1 if P is not None else 0]["bytes_out"], 4)
             r["pass_ms_over_level2"] = round(r["pass_ms_min"] / rows[1 if P is not None else 0]["pass_ms_min"], 3)
-            if g == (8, 32):
+            if g in ((8, 32), (8, 32, 1)):
                 r["slots_equal_level2"] = s == base
             rows.append(r)
         if P is not None:
