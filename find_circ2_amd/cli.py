@@ -370,6 +370,17 @@ def _bam_device(options):
                 **(dict(passes=passes) if passes is not None else {}))
 
 
+def _bam_encode(options):
+    """spliced_alignments.bam's records encoded from a SAM input's lines on the GPU (DESIGN.md §5 "BAM records
+    from SAM text on the device"): only with FC2_GPU_BAM_ENCODE=1, on the first of the run's devices, waiting at
+    most FC2_GPU_BAM_TIMEOUT_S seconds (60) for it; with FC2_GPU_BAM=1 or the zlib writer alike.  Unset, 0 or
+    anything else: None, the reading thread encodes every line itself."""
+    if os.environ.get("FC2_GPU_BAM_ENCODE") != "1":
+        return None
+    from .ctxpipe import device_index
+    return dict(mode=1, device=device_index(options.device), timeout_s=float(os.environ.get("FC2_GPU_BAM_TIMEOUT_S") or 0))
+
+
 def _bam_tiles_note(bam_device) -> str:
     """run.log's note of a tile below the block (0xff00, the command line's) and of its history."""
     tile, hist = (int(bam_device.get(k) or 0) for k in ("tile", "hist")) if bam_device else (0, 0)
@@ -405,6 +416,7 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                          if genome_eval is not None else {}),
                       gpu_group=_gpu_group(),
                       bam_device=_bam_device(options) if genome_eval is not None and bam_path else None,
+                      bam_encode=_bam_encode(options) if genome_eval is not None and bam_path else None,
                       **(_gzip_device(options) if genome_eval is not None and reads_gz else {}))
     try:
         try:
@@ -461,6 +473,8 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
             startup.update(zip(("gzip_gpu_pieces", "gzip_cpu_pieces"), nc.reads_gz_counts()))
             if nc.bam_device:
                 startup.update(zip(("bam_gpu_pieces", "bam_cpu_pieces"), nc.bam_out_pieces))
+            if nc.bam_encode:
+                startup.update(zip(("bam_enc_gpu_batches", "bam_enc_host_batches"), nc.bam_encode_batches))
             levels = (", gzip_gpu_level=2" if nc.gzip_device is not None and nc.gzip_level == 2 else "") + \
                 (", gzip_gpu_history=%d" % nc.gzip_history if nc.gzip_device is not None and nc.gzip_history > 0 else "") + \
                 (", bam_gpu_level=2" if nc.bam_device and nc.bam_device.get("level") == 2 else "") + _bam_tiles_note(nc.bam_device) + \

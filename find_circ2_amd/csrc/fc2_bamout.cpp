@@ -255,6 +255,10 @@ struct Writer {
         buf.clear();
         return ok;
     }
+    // the encode stage (attach_sam_stage): SAM lines go to it, and come back as records through add
+    SamStage *sam = nullptr;
+    bool add_sam(const char *line, const char *end, std::string &err) { return sam->add(line, end, err); }
+
     bool add(const char *p, size_t n) {
         if (mode) return add_piece(p, n);
         while (n) {
@@ -339,8 +343,16 @@ bool write_bulk(Writer *w, const char *p, size_t n, int threads) {
 
 bool write_sam(Writer *w, const char *line, const char *end, const std::unordered_map<std::string, int> &tid_of,
                std::string &err) {
+    if (w->sam) return w->add_sam(line, end, err);
     std::string rec;
     return encode_sam(line, end, tid_of, rec, err) && w->add(rec.data(), rec.size());
+}
+
+void attach_sam_stage(Writer *w, SamStage *stage) { w->sam = stage; }
+bool sam_stage_set(const Writer *w) { return w && w->sam != nullptr; }
+void sam_stage_counts(const Writer *w, uint64_t &gpu_batches, uint64_t &host_batches) {
+    gpu_batches = host_batches = 0;
+    if (w && w->sam) w->sam->counts(gpu_batches, host_batches);
 }
 
 bool encode_sam(const char *line, const char *end, const std::unordered_map<std::string, int> &tid_of,
@@ -512,9 +524,22 @@ void device_counts(const Writer *w, uint64_t &gpu_pieces, uint64_t &cpu_pieces) 
     cpu_pieces = w ? w->cpu_pieces : 0;
 }
 
-bool close_writer(Writer *w, std::string &err, uint64_t *gpu_pieces, uint64_t *cpu_pieces) {
+bool close_writer(Writer *w, std::string &err, uint64_t *gpu_pieces, uint64_t *cpu_pieces, uint64_t *enc_gpu,
+                  uint64_t *enc_host) {
     if (!w) return true;
+    std::string sam_err;
+    bool sam_ok = true;
+    if (w->sam) {                              // the lines it still holds become records before the last flush
+        sam_ok = w->sam->finish(sam_err);
+        uint64_t g = 0, c = 0;
+        w->sam->counts(g, c);
+        if (enc_gpu) *enc_gpu = g;
+        if (enc_host) *enc_host = c;
+        delete w->sam;
+        w->sam = nullptr;
+    }
     bool ok = w->mode ? w->drain() : w->flush_block();
+    ok = ok && sam_ok;
     if (gpu_pieces) *gpu_pieces = w->gpu_pieces;
     if (cpu_pieces) *cpu_pieces = w->cpu_pieces;
     if (w->gpu) bgz::gpu_close(w->gpu);        // (a device that timed out is left alone)
@@ -523,7 +548,8 @@ bool close_writer(Writer *w, std::string &err, uint64_t *gpu_pieces, uint64_t *c
     if (fwrite(eof, 1, sizeof eof, w->fp) != sizeof eof) ok = false;
     if (fclose(w->fp) != 0) ok = false;
     deflateEnd(&w->zs);
-    if (!ok) err = w->timed_out ? "IOError: writing spliced_alignments.bam failed: " + w->dev_err : "IOError: writing spliced_alignments.bam failed";
+    if (!sam_ok && !sam_err.empty()) err = sam_err;
+    else if (!ok) err = w->timed_out ? "IOError: writing spliced_alignments.bam failed: " + w->dev_err : "IOError: writing spliced_alignments.bam failed";
     delete w;
     return ok;
 }

@@ -49,9 +49,36 @@ bool set_device(Writer *w, int mode, int device, uint32_t block, uint32_t piece_
 bool device_set(const Writer *w);              // set_device has put the writer into mode 1 or 2
 // pieces written from the device (or the host model), and pieces of the device mode zlib compressed, so far
 void device_counts(const Writer *w, uint64_t &gpu_pieces, uint64_t &cpu_pieces);
-// flush (the device mode: the rest as a last piece, then every piece in flight, in order), EOF block, close;
-// false on an I/O error or a device that timed out; gpu_pieces, cpu_pieces (may be null): device_counts at the end
-bool close_writer(Writer *w, std::string &err, uint64_t *gpu_pieces = nullptr, uint64_t *cpu_pieces = nullptr);
+// The encode stage (fc2_ingest_set_bam_out_encode; fc2_bamout_sam.cpp makes one and attaches it): with a stage
+// attached write_sam hands every line to it (Writer::add_sam) instead of encoding it in place, and the stage
+// gives the records back through write_raw, in the lines' order, whenever it has a batch of them.  The writer
+// owns the stage: close_writer finishes it (the rest of the lines, every batch in flight) before its own flush
+// and deletes it.  An interface, so that this file links against nothing of the stage's.
+struct SamStage {
+    virtual ~SamStage() {}
+    // one line; false and err: a line encode_sam fails on (its message), the device timed out, or an I/O error
+    // (err left empty) -- now or for a line taken earlier
+    virtual bool add(const char *line, const char *end, std::string &err) = 0;
+    virtual bool finish(std::string &err) = 0;
+    // batches written as the device (or its stand-in) returned them, and batches encoded line by line
+    virtual void counts(uint64_t &gpu_batches, uint64_t &host_batches) const = 0;
+};
+void attach_sam_stage(Writer *w, SamStage *stage);
+bool sam_stage_set(const Writer *w);
+void sam_stage_counts(const Writer *w, uint64_t &gpu_batches, uint64_t &host_batches);
+// mode 1: the lines encoded on GPU `device` (fc2_sam_enc_gpu.h); 2: by fc2_sam_encode_host in its place; batches
+// of max_lines lines and max_text bytes (0: 16384, 4 MiB), a wait for the device at most timeout_s seconds (0:
+// 60).  names: the header's reference names in order; tid_of: the map encode_sam is given, which must outlive
+// the writer.  Call after open_writer (and set_device, if that is called) and before the first record
+bool set_encode(Writer *w, int mode, int device, const std::vector<std::string> &names,
+                const std::unordered_map<std::string, int> *tid_of, uint32_t max_lines, uint32_t max_text, double timeout_s,
+                std::string &err);
+// flush (the encode stage finished first; the device mode: the rest as a last piece, then every piece in flight,
+// in order), EOF block, close; false on an I/O error, a device that timed out or a line the stage still had that
+// encode_sam fails on (err: its message); gpu_pieces, cpu_pieces (may be null): device_counts at the end;
+// enc_gpu, enc_host (may be null): sam_stage_counts at the end
+bool close_writer(Writer *w, std::string &err, uint64_t *gpu_pieces = nullptr, uint64_t *cpu_pieces = nullptr,
+                  uint64_t *enc_gpu = nullptr, uint64_t *enc_host = nullptr);
 
 }  // namespace bam
 }  // namespace fc2

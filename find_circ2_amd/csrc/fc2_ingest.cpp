@@ -646,6 +646,9 @@ struct fc2_ingest {
     uint32_t bam_tile = 0, bam_hist = 0;        // fc2_ingest_set_bam_out_device_tiles
     uint32_t bam_depth = 0, bam_nice = 0;       // fc2_ingest_set_bam_out_device_search (0, 0: the level's own)
     uint32_t bam_passes = 0;                    // fc2_ingest_set_bam_out_device_passes (0: one)
+    uint32_t bam_enc_lines = 0, bam_enc_text = 0;       // fc2_ingest_set_bam_out_encode_caps (0: the rule's own)
+    double bam_enc_timeout = 0;
+    uint64_t bam_enc_gpu = 0, bam_enc_host = 0;         // fc2_ingest_bam_encode_counts, once the writer is closed
     // grouping state
     bool started = false;
     Mate current, other;
@@ -2481,10 +2484,50 @@ extern "C" int fc2_ingest_bam_out_counts(const fc2_ingest *h, uint64_t *gpu_piec
     return FC2_OK;
 }
 
+extern "C" int fc2_ingest_set_bam_out_encode_caps(fc2_ingest *h, uint32_t max_lines, uint32_t max_text, double timeout_s) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_encode_caps: null argument");
+    if (!h->bam_out || h->n_records || fc2::bam::sam_stage_set(h->bam_out))
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_encode_caps: call after fc2_ingest_set_bam_out, before "
+                                      "fc2_ingest_set_bam_out_encode and before reading");
+    if (max_lines > FC2_SAM_ENC_MAX_LINES || max_text > FC2_SAM_ENC_MAX_TEXT || !(timeout_s >= 0))
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_encode_caps: a batch is at most 16384 lines and 4 MiB of text, "
+                                      "the timeout not negative");
+    h->bam_enc_lines = max_lines;
+    h->bam_enc_text = max_text;
+    h->bam_enc_timeout = timeout_s;
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_set_bam_out_encode(fc2_ingest *h, int mode, int device) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_encode: null argument");
+    if (!h->bam_out || h->n_records)
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_encode: call after fc2_ingest_set_bam_out, before reading");
+    if (mode < 0 || mode > 2 || (mode == 1 && device < 0))
+        return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_encode: mode is 0, 1 or 2");
+    if (fc2::bam::sam_stage_set(h->bam_out)) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_bam_out_encode: call once");
+    if (h->bam || !mode) return FC2_OK;         // (BAM input: its records are copied, there is nothing to encode)
+    std::string err;
+    if (!fc2::bam::set_encode(h->bam_out, mode, device, h->refs, &h->tid_of, h->bam_enc_lines, h->bam_enc_text,
+                              h->bam_enc_timeout, err))
+        return fc2::fail(mode == 1 ? FC2_E_HIP : FC2_E_PARAM, "fc2_ingest_set_bam_out_encode: " + err);
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_bam_encode_counts(const fc2_ingest *h, uint64_t *gpu_batches, uint64_t *host_batches) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_bam_encode_counts: null argument");
+    // (they outlive fc2_ingest_close_bam_out, which encodes the last batches)
+    uint64_t g = h->bam_enc_gpu, c = h->bam_enc_host;
+    if (h->bam_out && fc2::bam::sam_stage_set(h->bam_out)) fc2::bam::sam_stage_counts(h->bam_out, g, c);
+    if (gpu_batches) *gpu_batches = g;
+    if (host_batches) *host_batches = c;
+    return FC2_OK;
+}
+
 extern "C" int fc2_ingest_close_bam_out(fc2_ingest *h) {
     if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_close_bam_out: null argument");
     std::string err;
-    const bool ok = fc2::bam::close_writer(h->bam_out, err, &h->bam_gpu_pieces, &h->bam_cpu_pieces);
+    const bool ok = fc2::bam::close_writer(h->bam_out, err, &h->bam_gpu_pieces, &h->bam_cpu_pieces, &h->bam_enc_gpu,
+                                           &h->bam_enc_host);
     h->bam_out = nullptr;
     return ok ? FC2_OK : fc2::fail(FC2_E_IO, err);
 }

@@ -49,15 +49,25 @@ class NativeIngest:
                 frags.append([parse_sam_line(l, self.tid_of) for l in block.split("\n") if l])
         return frags
 
-    def set_bam_out(self, path: str, bam_device=None):
+    def set_bam_out(self, path: str, bam_device=None, bam_encode=None):
         """-B/--bam: anchor alignments to ``path`` (include/fc2_ingest.h).  bam_device: None, or the
         arguments of fc2_ingest_set_bam_out_device as a dict -- mode (1: the records compressed on GPU
         ``device``; 2: by the host model of it, a test setting), device, block, piece_blocks, timeout_s
         (each 0 or absent: the default), level (the GPU compressor's, 1 or 2; absent: 1), tile and hist
-        (fc2_ingest_set_bam_out_device_tiles; absent or 0: a block is one tile)."""
+        (fc2_ingest_set_bam_out_device_tiles; absent or 0: a block is one tile).  bam_encode: None, or the
+        arguments of fc2_ingest_set_bam_out_encode as a dict -- mode (1: a SAM input's written records encoded
+        on GPU ``device``; 2: by the host rule in its place, a test setting), device, and max_lines, max_text,
+        timeout_s (fc2_ingest_set_bam_out_encode_caps; each 0 or absent: the default)."""
         N.check(N.lib().fc2_ingest_set_bam_out(self.h, path.encode()))
         if bam_device:
             set_bam_out_device(self.h, bam_device)
+        if bam_encode:
+            set_bam_out_encode(self.h, bam_encode)
+
+    def bam_encode_counts(self) -> Tuple[int, int]:
+        """(batches of SAM lines written as the device encoded them, batches encoded line by line on the
+        host); final after close_bam_out, (0, 0) without bam_encode."""
+        return bam_encode_counts(self.h)
 
     def bam_out_counts(self) -> Tuple[int, int]:
         """(pieces of spliced_alignments.bam the device compressed, pieces of the device mode zlib
@@ -154,6 +164,21 @@ def set_bam_out_device(h, bam_device) -> None:
         N.check(N.lib().fc2_ingest_set_bam_out_device_tiles(h, int(d.get("tile", 0)), int(d.get("hist", 0))))
     N.check(N.lib().fc2_ingest_set_bam_out_device(h, int(d.get("mode", 1)), int(d.get("device", 0)), int(d.get("block", 0)),
                                                   int(d.get("piece_blocks", 0)), float(d.get("timeout_s", 0.0))))
+
+
+def set_bam_out_encode(h, bam_encode) -> None:
+    """fc2_ingest_set_bam_out_encode on the ingest handle ``h`` (NativeIngest.set_bam_out's bam_encode)."""
+    d = dict(bam_encode)
+    if d.get("max_lines") or d.get("max_text") or d.get("timeout_s"):
+        N.check(N.lib().fc2_ingest_set_bam_out_encode_caps(h, _u32(d.get("max_lines"), 0), _u32(d.get("max_text"), 0),
+                                                           float(d.get("timeout_s") or 0.0)))
+    N.check(N.lib().fc2_ingest_set_bam_out_encode(h, int(d.get("mode", 1)), int(d.get("device", 0))))
+
+
+def bam_encode_counts(h) -> Tuple[int, int]:
+    g, c = ctypes.c_uint64(), ctypes.c_uint64()
+    N.check(N.lib().fc2_ingest_bam_encode_counts(h, ctypes.byref(g), ctypes.byref(c)))
+    return int(g.value), int(c.value)
 
 
 def bam_out_counts(h) -> Tuple[int, int]:

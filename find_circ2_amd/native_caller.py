@@ -75,7 +75,7 @@ class NativeCaller:
                  bam_out: str = "", reads_gz=None, inflate_device=None, inflate_after: int = 0,
                  gzip_device=None, gzip_tile: int = 0, gzip_timeout_s: float = 0.0, gpu_walk: bool = True,
                  gpu_digest: bool = False, gpu_group: int = 0, bam_device=None, gzip_level: int = 1,
-                 gzip_history: int = 0, gzip_search=None, gzip_passes=None):
+                 gzip_history: int = 0, gzip_search=None, gzip_passes=None, bam_encode=None):
         o = copts
         # the strings must outlive the handle's open call (fc2_caller_open copies them)
         self._keep = [o.name.encode(), known_circ.encode() if known_circ else None,
@@ -95,6 +95,8 @@ class NativeCaller:
         self.bam_out = bam_out
         self.bam_device = bam_device   # spliced_alignments.bam's records compressed on a GPU (ingest.set_bam_out_device's dict)
         self.bam_out_pieces = (0, 0)   # ... (pieces from the device, pieces zlib compressed), once close_bam_out ran
+        self.bam_encode = bam_encode   # a SAM input's written records encoded on a GPU (ingest.set_bam_out_encode's dict)
+        self.bam_encode_batches = (0, 0)   # ... (batches from the device, batches the host encoded), once close_bam_out ran
         self.reads_gz = reads_gz    # (path, level, threads, piece): spliced_reads.fastq.gz written natively
         self.inflate_device = inflate_device   # a BGZF input's blocks inflated on this GPU (None: the CPU)
         self.inflate_after = inflate_after     # ... once this many bytes of the input were read
@@ -127,6 +129,11 @@ class NativeCaller:
             if self.bam_device:
                 from .ingest import set_bam_out_device
                 set_bam_out_device(ing, self.bam_device)
+            if self.bam_encode and self.format != "sam":
+                self.bam_encode = None     # a BAM input's records are copied: nothing to encode, nothing counted
+            if self.bam_encode:
+                from .ingest import set_bam_out_encode
+                set_bam_out_encode(ing, self.bam_encode)
         if self.inflate_device is not None:
             N.check(L.fc2_ingest_set_gpu_inflate_from(ing, int(self.inflate_device), int(self.inflate_after)))
             N.check(L.fc2_ingest_set_gpu_walk(ing, int(bool(self.gpu_walk))))
@@ -172,6 +179,9 @@ class NativeCaller:
             if self.bam_device:
                 from .ingest import bam_out_counts
                 self.bam_out_pieces = bam_out_counts(ing)
+            if self.bam_encode:
+                from .ingest import bam_encode_counts
+                self.bam_encode_batches = bam_encode_counts(ing)
 
     def inflate_counts(self):
         """(BGZF blocks inflated on the GPU, on the CPU) since the GPU inflate was set (0, 0 without)."""

@@ -284,6 +284,79 @@ int fc2_ingest_set_gpu_group(fc2_ingest *h, int on);
  * run ahead of the reader, the second is the reader's n_reads less the first (0 while that is negative),
  * so before the end the two need not add up to the fragments read so far. */
 int fc2_ingest_group_counts(const fc2_ingest *h, uint64_t *device_fragments, uint64_t *host_fragments);
+
+/* ---- -B's BAM records from SAM text on the GPU (csrc/fc2_sam_encode_impl.h, fc2_sam_encode.hip) ----
+ * A batch of SAM lines (back to back, no newlines; line i is text[off[i] .. off[i + 1])) becomes the BAM
+ * record bytes the -B encoder above (fc2::bam::encode_sam) makes of them.  The contract is "never a wrong
+ * byte": for every line either status[i] != 0 (one of the reasons below) and size[i] == 0, or the record's
+ * bytes, its 4-byte block_size included, are encode_sam's and encode_sam succeeds on the line.  What the rule
+ * does not reproduce exactly it refuses; the caller encodes such lines on the host. */
+#define FC2_SAM_ENC_OK        0u
+#define FC2_SAM_ENC_FIELDS    1u  /* fewer than 11 fields */
+#define FC2_SAM_ENC_NUMBER    2u  /* FLAG, POS, MAPQ, PNEXT or TLEN is not -?[0-9]{1,9} */
+#define FC2_SAM_ENC_CIGAR     3u  /* not `*` or ([0-9]{1,9}[MIDNSHP=X])+, a count of 2^28 or more, over 65535 ops */
+#define FC2_SAM_ENC_QNAME     4u  /* QNAME is empty or longer than 254 bytes */
+#define FC2_SAM_ENC_TAG       5u  /* a tag that is not TG:T:VALUE, an `i` value that is not -?[0-9]{1,18} */
+#define FC2_SAM_ENC_TAG_TYPE  6u  /* a tag of type f or B (left to the host), or of no known type */
+#define FC2_SAM_ENC_OFFSETS   7u  /* off[i] > off[i + 1], or off[i + 1] > text_bytes */
+#define FC2_SAM_ENC_LONG      8u  /* fc2_gpu_sam_encode only: a line longer than a batch's text */
+/* a batch: at most this many lines and this many bytes of text */
+#define FC2_SAM_ENC_MAX_LINES 16384u
+#define FC2_SAM_ENC_MAX_TEXT  (4u << 20)
+/* Bytes the records of n_lines lines in text_bytes bytes of text take at most: 2 * text_bytes + 40 * n_lines
+ * (proved beside fc2::samenc::record_bound in csrc/fc2_sam_encode_impl.h). */
+#define FC2_SAM_ENC_BOUND(text_bytes, n_lines) (2ull * (text_bytes) + 40ull * (n_lines))
+/* The table RNAME and RNEXT are looked up in, made of the header's reference names in their order: a name's
+ * id is its index, and of a name that occurs twice the last index counts (as in the ingest's own map).  lens
+ * may be null (the names are C strings).  table null or cap below the need: only *need (bytes, a multiple of
+ * 4) is set and FC2_E_RANGE returned if table was given.  The table is position independent: copy it to the
+ * device as it is. */
+int fc2_sam_names_table(const char *const *names, const uint32_t *lens, uint32_t n_names, uint32_t *table,
+                        uint64_t cap, uint64_t *need);
+/* One batch on the device (all pointers device memory; n_lines 1..FC2_SAM_ENC_MAX_LINES, text_bytes at most
+ * FC2_SAM_ENC_MAX_TEXT, out_cap at least FC2_SAM_ENC_BOUND(text_bytes, n_lines)): a sizing pass (status[i],
+ * size[i]), an exclusive scan (out_off[0 .. n_lines], *total = out_off[n_lines]) and a writing pass that puts
+ * the accepted records back to back in line order, record i at out + out_off[i].  A wavefront a line.  No
+ * byte of out at or past *total is written; nothing outside the line is read. */
+int fc2_sam_encode_launch(const uint8_t *text, uint32_t text_bytes, const uint32_t *off, uint32_t n_lines,
+                          const uint32_t *names_table, uint32_t table_bytes, uint8_t *out, uint64_t out_cap,
+                          uint32_t *out_off, uint32_t *size, uint32_t *status, uint32_t *total, void *stream);
+/* The same rule on host memory (the tests' oracle for the kernels, and the writer's stand-in mode). */
+int fc2_sam_encode_host(const uint8_t *text, uint32_t text_bytes, const uint32_t *off, uint32_t n_lines,
+                        const uint32_t *names_table, uint32_t table_bytes, uint8_t *out, uint64_t out_cap,
+                        uint32_t *out_off, uint32_t *size, uint32_t *status, uint32_t *total);
+/* Any number of lines through the writer's slot pipeline on GPU `device` (four slots, each with its stream:
+ * upload, the three kernels, download of the total, the statuses and exactly the total's bytes), in batches of
+ * batch_lines lines (0: FC2_SAM_ENC_MAX_LINES) and at most FC2_SAM_ENC_MAX_TEXT bytes: status[i] for every
+ * line, the accepted records back to back in line order in out (cap at least fc2_gpu_sam_encode_bound), their
+ * bytes in *out_n.  names: n_names C strings. */
+int fc2_gpu_sam_encode(int device, const void *text, const uint32_t *off, uint64_t n_lines, const char *const *names,
+                       uint32_t n_names, uint32_t batch_lines, void *out, uint64_t cap, uint64_t *out_n, uint32_t *status);
+uint64_t fc2_gpu_sam_encode_bound(uint64_t text_bytes, uint64_t n_lines);
+/* The yardstick: one line through the -B encoder itself (fc2::bam::encode_sam, whose body this does not
+ * change).  FC2_E_FORMAT and encode_sam's message (fc2_last_error) where it fails; FC2_E_RANGE if cap is
+ * below the record's bytes (*out_n is set all the same). */
+int fc2_sam_encode_line(const char *line, uint64_t n, const char *const *names, uint32_t n_names, void *out,
+                        uint64_t cap, uint64_t *out_n);
+/* -B with SAM input: the written records encoded in batches by the rule above instead of line by line on the
+ * reading thread.  Call after fc2_ingest_set_bam_out and before reading.  mode 0: off (the default); 1: GPU
+ * `device`; 2: fc2_sam_encode_host in the device's place, through the same batching, ordering, refusal and
+ * error code (a test setting).  Lines fill a batch; a full batch goes to one of four slots; batches are
+ * collected strictly in order.  A batch with no refusal is written as it came back; a batch with one is
+ * encoded again on the host, line by line, so the file's bytes and order are those of mode 0 always.  A line
+ * the -B encoder fails on ends the run with the code and message of mode 0, at a later fc2_ingest_next or at
+ * fc2_ingest_close_bam_out: the records before it are in the file, none after it.  A device that fails moves
+ * that batch and every later one to the host; one that does not answer within the timeout ends the run with
+ * FC2_E_IO.  BAM input takes the call and does nothing (its records are copied).  Works with either writer
+ * (fc2_ingest_set_bam_out_device or zlib). */
+int fc2_ingest_set_bam_out_encode(fc2_ingest *h, int mode, int device);
+/* A batch's caps (0: FC2_SAM_ENC_MAX_LINES, FC2_SAM_ENC_MAX_TEXT; never more) and the seconds a wait for the
+ * device may take (0: 60), for the stage set afterwards with fc2_ingest_set_bam_out_encode.  The command line
+ * passes FC2_GPU_BAM_TIMEOUT_S here. */
+int fc2_ingest_set_bam_out_encode_caps(fc2_ingest *h, uint32_t max_lines, uint32_t max_text, double timeout_s);
+/* batches written as the device (mode 2: the host rule) returned them, and batches encoded line by line on
+ * the host; final after fc2_ingest_close_bam_out (0, 0 while the stage is off) */
+int fc2_ingest_bam_encode_counts(const fc2_ingest *h, uint64_t *gpu_batches, uint64_t *host_batches);
 #ifdef __cplusplus
 }
 #endif
