@@ -9,6 +9,7 @@ from find_circ2_amd import _native as N
 E_PARAM, E_FORMAT, E_RANGE, E_IO = -1, -3, -4, -5     # include/fc2_bp.h
 CANARY = 0xC3
 MAX_LINES, MAX_TEXT = 16384, 4 << 20
+ENC_OFFSETS, ENC_LONG = 7, 8                          # FC2_SAM_ENC_OFFSETS, FC2_SAM_ENC_LONG (include/fc2_ingest.h)
 # "dup" twice: the last one's index counts, as in the ingest's own map
 NAMES = [b"chr1", b"chr2", b"chrX", b"dup", b"chr3", b"dup"]
 
@@ -38,12 +39,10 @@ def pack(lines):
     return text, off
 
 
-def encode_host(lines, names=NAMES, table=None):
-    """fc2_sam_encode_host on one batch: (status, size, out_off, total, the output with 64 canary bytes after
-    the bound)."""
-    text, off = pack(lines)
-    table = names_table(names) if table is None else table
-    n, nb = len(lines), int(off[-1])
+def encode_host_packed(text, nb, off, table):
+    """fc2_sam_encode_host on `nb` bytes of text under any len(off) - 1 offsets, ascending or not: (status, size,
+    out_off, total, the output with 64 canary bytes after the bound)."""
+    n = len(off) - 1
     cap = bound(nb, n)
     out = np.full(cap + 64, CANARY, np.uint8)
     status, size = np.full(n, 0xDEADBEEF, np.uint32), np.full(n, 0xDEADBEEF, np.uint32)
@@ -54,11 +53,23 @@ def encode_host(lines, names=NAMES, table=None):
     return status, size, out_off, int(total.value), out
 
 
+def encode_host(lines, names=NAMES, table=None):
+    """encode_host_packed on one batch of lines."""
+    text, off = pack(lines)
+    return encode_host_packed(text, int(off[-1]), off, names_table(names) if table is None else table)
+
+
 def encode_host_all(lines, names=NAMES):
-    """encode_host over any number of lines, in batches the rule takes: (status list, record-or-None list)."""
+    """encode_host over any number of lines, in batches the rule takes: (status list, record-or-None list).  A line
+    no batch holds ends the batch before it and is FC2_SAM_ENC_LONG, as in fc2_gpu_sam_encode."""
     table = names_table(names)
     st, recs, i = [], [], 0
     while i < len(lines):
+        if len(lines[i]) > MAX_TEXT:
+            st.append(ENC_LONG)
+            recs.append(None)
+            i += 1
+            continue
         j, nb = i, 0
         while j < len(lines) and j - i < MAX_LINES and nb + len(lines[j]) <= MAX_TEXT:
             nb += len(lines[j])
@@ -144,6 +155,40 @@ def planted_lines():
     L += [sam_line(tags=[b"XZ:Z:"]), sam_line(tags=[b"XZ:Z:" + b"z" * 200]), sam_line(tags=[b"XH:H:1AE301"])]
     L.append(sam_line(tags=[b"NM:i:2", b"MD:Z:10A5^AC6", b"AS:i:94", b"XS:i:0", b"SA:Z:chr2,500,+,50M50S,60,1;", b"XA:A:q"]))
     L += [sam_line(qname=b"q"), sam_line(qname=b"n" * 254)]
+    return L + lane_boundary_lines()
+
+
+def _letters(n, first=0):
+    """n bytes no two neighbours of which are equal, so a byte a lane off is a wrong byte."""
+    return bytes(65 + (first + k) % 26 + 32 * ((first + k) // 26 % 2) for k in range(n))
+
+
+def lane_boundary_lines():
+    """Accepted lines whose runs of bytes end around the 64 lanes a wavefront loads and stores with: the name, Z and
+    H values, CIGAR ops, a QUAL shorter than SEQ, tabs at bytes 63, 64 and 65 of the line, and a 64th tag."""
+    rng = np.random.default_rng(12)
+    L = []
+    for n in (63, 64, 65, 127, 128):
+        L.append(sam_line(qname=_letters(n, n), tags=[b"NM:i:%d" % n]))
+    for n in (63, 64, 65, 127, 128, 129):
+        L.append(sam_line(tags=[b"XZ:Z:" + _letters(n, n), b"NM:i:1"]))
+        L.append(sam_line(tags=[b"XH:H:" + bytes(b"0123456789ABCDEF"[(k * 7 + n) % 16] for k in range(n)), b"XA:A:e"]))
+        L.append(sam_line(tags=[b"NM:i:300", b"XZ:Z:" + _letters(n, 3), b"XH:H:" + b"1A" * (n // 2) + b"F" * (n % 2)]))
+    for n in (63, 64, 65, 128, 129):
+        L.append(sam_line(cigar=b"".join(b"%d%c" % (1 + (k * 5 + n) % 300, b"MIDNSHP=X"[(k + n) % 9]) for k in range(n))))
+    for n in (64, 65, 129):
+        for short in (1, 64):
+            L.append(sam_line(seq=_seq(n, rng), qual=bytes(33 + int(q) for q in rng.integers(0, 42, n - short)),
+                              cigar=b"%dM" % n))
+    # tab 1, 5 or 10 of the line at its byte 63, 64 or 65 (from 0): a longer name moves them there
+    for tab in (1, 5, 10):
+        before = len(b"\t".join(sam_line(qname=b"").split(b"\t")[:tab]))       # the tab's place under an empty name
+        for at in (63, 64, 65):
+            line = sam_line(qname=_letters(at - before, tab))
+            assert [i for i, c in enumerate(line) if c == 9][tab - 1] == at
+            L.append(line)
+    L.append(sam_line(tags=[b"X%c:A:%c" % (48 + k % 10, 65 + k % 26) if k % 3 else b"Y%c:i:%d" % (97 + k % 26, k * 1021 - 30000)
+                            for k in range(63)] + [b"NM:i:64"]))
     return L
 
 
@@ -165,22 +210,23 @@ def refused_lines():
     return R
 
 
-def bwa_lines(n, seed=5):
-    """bwa-mem-shaped lines: 100-base reads, 5 tags, about 320 bytes."""
+def bwa_lines(n, seed=5, read_len=100):
+    """bwa-mem-shaped lines: reads of read_len bases, 5 tags, about 320 bytes at 100 bases (220 at 50)."""
     rng = np.random.default_rng(seed)
+    R = read_len
     out = []
     for k in range(n):
-        s = int(rng.integers(0, 60))
-        cigar = b"100M" if s < 20 else b"%dM%dS" % (100 - s, s) if s < 40 else b"%dS%dM" % (s, 100 - s)
+        s = int(rng.integers(0, 3 * R // 5))
+        cigar = b"%dM" % R if s < R // 5 else b"%dM%dS" % (R - s, s) if s < 2 * R // 5 else b"%dS%dM" % (s, R - s)
         chrom = NAMES[int(rng.integers(0, 5))]
         pos = int(rng.integers(1, 10 ** 8))
-        tags = [b"NM:i:%d" % rng.integers(0, 4), b"MD:Z:%d" % (100 - s), b"AS:i:%d" % (100 - s), b"XS:i:%d" % rng.integers(0, 60),
-                b"SA:Z:%s,%d,%s,%dS%dM,%d,0;" % (chrom, pos + 2000, b"+-"[k & 1:][:1], 100 - s, s or 1, rng.integers(0, 61))]
+        tags = [b"NM:i:%d" % rng.integers(0, 4), b"MD:Z:%d" % (R - s), b"AS:i:%d" % (R - s), b"XS:i:%d" % rng.integers(0, 60),
+                b"SA:Z:%s,%d,%s,%dS%dM,%d,0;" % (chrom, pos + 2000, b"+-"[k & 1:][:1], R - s, s or 1, rng.integers(0, 61))]
         out.append(sam_line(qname=b"SRR1000000.%d" % (k // 2), flag=b"%d" % rng.choice([0, 16, 65, 129, 2048, 2064, 83, 163]),
                             rname=chrom, pos=b"%d" % pos, mapq=b"%d" % rng.integers(0, 61), cigar=cigar,
                             rnext=rng.choice([b"=", b"*", b"chr2"]), pnext=b"%d" % rng.integers(0, 10 ** 8),
-                            tlen=b"%d" % rng.integers(-500, 500), seq=_seq(100, rng),
-                            qual=bytes(33 + int(q) for q in rng.integers(2, 42, 100)), tags=tags))
+                            tlen=b"%d" % rng.integers(-500, 500), seq=_seq(R, rng),
+                            qual=bytes(33 + int(q) for q in rng.integers(2, 42, R)), tags=tags))
     return out
 
 
