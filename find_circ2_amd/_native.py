@@ -164,6 +164,7 @@ EXPORTED = [
     "fc2_ingest_set_bam_out_device_passes",
     "fc2_sam_names_table", "fc2_sam_encode_launch", "fc2_sam_encode_host", "fc2_gpu_sam_encode", "fc2_gpu_sam_encode_bound",
     "fc2_sam_encode_line", "fc2_ingest_set_bam_out_encode", "fc2_ingest_set_bam_out_encode_caps", "fc2_ingest_bam_encode_counts",
+    "fc2_sam_group_launch", "fc2_sam_group_host", "fc2_ingest_set_gpu_sam_group", "fc2_ingest_sam_group_counts",
     # include/fc2_caller.h
     "fc2_caller_open", "fc2_caller_set_genome", "fc2_caller_inflate_counts", "fc2_caller_ingest", "fc2_caller_close", "fc2_caller_next",
     "fc2_caller_submit", "fc2_caller_submit_compact", "fc2_caller_submit_long", "fc2_caller_queued", "fc2_caller_take", "fc2_caller_rows", "fc2_caller_write_rows", "fc2_caller_counter", "fc2_caller_stats",
@@ -392,6 +393,10 @@ def lib() -> ctypes.CDLL:
         "fc2_sam_encode_host": (ctypes.c_int, [vp, u32, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp]),
         "fc2_gpu_sam_encode": (ctypes.c_int, [ctypes.c_int, vp, vp, u64, P(ctypes.c_char_p), u32, u32, vp, u64, P(u64), vp]),
         "fc2_gpu_sam_encode_bound": (u64, [u64, u64]),
+        "fc2_sam_group_launch": (ctypes.c_int, [vp, u32, vp, u32, vp, vp, vp, vp, u32, vp, vp]),
+        "fc2_sam_group_host": (ctypes.c_int, [vp, u32, vp, u32, vp, vp, vp, vp, u32]),
+        "fc2_ingest_set_gpu_sam_group": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
+        "fc2_ingest_sam_group_counts": (ctypes.c_int, [vp, P(u64), P(u64)]),
         "fc2_sam_encode_line": (ctypes.c_int, [ctypes.c_char_p, u64, P(ctypes.c_char_p), u32, vp, u64, P(u64)]),
         "fc2_ingest_set_bam_out_encode": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int]),
         "fc2_ingest_set_bam_out_encode_caps": (ctypes.c_int, [vp, u32, u32, ctypes.c_double]),

@@ -303,6 +303,17 @@ def _gpu_group():
     return 1 if os.environ.get("FC2_GPU_GROUP") == "1" else 0
 
 
+def _gpu_sam_group(options):
+    """Whether the first of the run's devices closes the unspliced fragments of a SAM text input, so the parse
+    threads step over their lines (DESIGN.md §5 "Unspliced fragments of SAM text closed on the device"):
+    (1, device) only with FC2_GPU_SAM_GROUP=1 -- off by default, and off at 0 or any other value.  A BAM input
+    ignores it (FC2_GPU_GROUP is its stage)."""
+    if os.environ.get("FC2_GPU_SAM_GROUP") != "1":
+        return 0
+    from .ctxpipe import device_index
+    return (1, device_index(options.device))
+
+
 def _search_env(prefix):
     """(depth, nice) of level 2's search effort from ``prefix``_DEPTH and ``prefix``_NICE (DESIGN.md §5 "Search
     effort at level 2"), or None with both unset or empty; one alone leaves the other at level 2's own (8, 32).
@@ -415,6 +426,7 @@ def _run_native_caller(options, path, is_bam, out, hp, logger, evaluator_factory
                               gpu_digest=_gpu_digest())
                          if genome_eval is not None else {}),
                       gpu_group=_gpu_group(),
+                      gpu_sam_group=_gpu_sam_group(options),
                       bam_device=_bam_device(options) if genome_eval is not None and bam_path else None,
                       bam_encode=_bam_encode(options) if genome_eval is not None and bam_path else None,
                       **(_gzip_device(options) if genome_eval is not None and reads_gz else {}))

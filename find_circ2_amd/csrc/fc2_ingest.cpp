@@ -40,6 +40,8 @@
 #include "fc2_deflate.h"
 #include "fc2_inflate.h"
 #include "fc2_ingest_impl.h"
+#include "fc2_sam_enc_gpu.h"
+#include "fc2_sam_group_gpu.h"
 
 using fc2::ing::Mate;
 using fc2::ing::MateRef;
@@ -630,6 +632,10 @@ struct fc2_ingest {
     // fragments the parse threads stepped over on those rows' word
     std::atomic<int> gpu_group{0};
     std::atomic<uint64_t> group_dev_frags{0};
+    // fc2_ingest_set_gpu_sam_group, SAM text (0 off, 1 GPU sam_group_device, 2 the host twin: a test setting); the
+    // stage itself is made with the parse-ahead threads (pull); the fragments stepped over on its rows' word
+    int sam_group = 0, sam_group_device = 0;
+    std::atomic<uint64_t> sam_group_dev_frags{0};
     std::atomic<int64_t> inflate_wait_ns{0};     // the reader's wait for inflated BGZF batches (timing)
     std::string z_err;
     // header
@@ -695,6 +701,13 @@ struct fc2_ingest::SamAhead {
     struct Batch {
         uint64_t seq = 0;
         std::string block;                      // the block's bytes (whole lines)
+        // or, with fc2_ingest_set_gpu_sam_group: the same bytes in a slot's pinned text (slot >= 0), the slot
+        // kept until the batch is taken again (the parsed records point into the text); rows: the slot's
+        // launches were queued and their rows are still to be collected
+        const char *stext = nullptr;
+        size_t slen = 0;
+        int slot = -1;
+        bool rows = false;
         // or, BGZF input (bgzf_split_loop): whole records in place in an inflated batch
         std::shared_ptr<const CharBuf> vbuf;
         size_t voff = 0, vlen = 0;
@@ -751,6 +764,7 @@ struct fc2_ingest::SamAhead {
     size_t max_pinned = 64;                     // pull stops there (FC2_PIN_MAX): few handed fragments
                                                 // must not pin the whole input
     bool stop = false;
+    fc2::samgrp::Stage *sam_stage = nullptr;    // fc2_ingest_set_gpu_sam_group: the blocks' rows (null: off)
     std::thread splitter;
     std::vector<std::thread> parsers;
     // the splitter waits for input in poll() on the input and this pipe, so closing the ingest
@@ -774,6 +788,7 @@ struct fc2_ingest::SamAhead {
         for (std::thread &t : parsers) t.join();
         for (int fd : wake)
             if (fd >= 0) close(fd);
+        fc2::samgrp::close(sam_stage);           // (the threads have joined: nobody holds a slot's text any more)
         if ((split_steps || split_jumps) && getenv("FC2_CALLER_TIMING"))   // (the splitter has joined)
             fprintf(stderr, "bgzf split: %llu records read one at a time, %llu jumps through the record lists\n",
                     (unsigned long long)split_steps, (unsigned long long)split_jumps);
@@ -1341,6 +1356,89 @@ int read_header(fc2_ingest *h) {
     return FC2_OK;
 }
 
+// a batch that leaves the flight gives its slot back (fc2_ingest_set_gpu_sam_group): its text is not read again
+void retire_slot(fc2_ingest::SamAhead &A, fc2_ingest::SamAhead::Batch &b) {
+    if (b.slot >= 0) fc2::samgrp::release(A.sam_stage, b.slot);
+    b.slot = -1;
+    b.stext = nullptr;
+    b.slen = 0;
+    b.rows = false;
+}
+
+// fc2_ingest_set_gpu_sam_group: the splitter's next block read straight into a slot's pinned text, cut after its
+// last newline as ever, and the slot's upload, launches and download queued.  1: the batch is ready (its text in
+// the slot; b.rows: rows will come); 2: the ingest is closing; 0: no slot is free, or the block outgrew the
+// slot's text before a newline came -- everything read so far is in `carry`, and the caller goes on as it does
+// without the stage.  The splitter never waits for the device.
+int sam_block_in_slot(fc2_ingest *h, fc2_ingest::SamAhead &A, fc2_ingest::SamAhead::Batch &b, std::string &carry, bool &in_eof) {
+    const size_t cap = fc2::samgrp::max_text(A.sam_stage);
+    // bytes that are here already (read with the header, or left by a block that went the other way) are cut like
+    // bytes that are read: a block ends after the first newline from its A.block-th byte on
+    size_t take = carry.size();
+    if (take >= A.block)
+        if (const void *nl = memchr(carry.data() + (A.block - 1), '\n', take - (A.block - 1)))
+            take = (size_t)((const char *)nl - carry.data()) + 1;
+    if (take > cap) return 0;
+    char *text = nullptr;
+    const int slot = fc2::samgrp::acquire(A.sam_stage, text);
+    if (slot < 0) return 0;
+    size_t len = take;
+    if (len) memcpy(text, carry.data(), len);
+    if (take < carry.size()) {                  // whole lines, and more behind them: nothing is read for this block
+        carry.erase(0, take);
+        b.block.clear();
+        b.stext = text;
+        b.slen = len;
+        b.slot = slot;
+        b.rows = fc2::samgrp::submit(A.sam_stage, slot, (uint32_t)len);
+        return 1;
+    }
+    bool has_nl = len && memchr(text, '\n', len) != nullptr;
+    while (!in_eof && (len < A.block || !has_nl)) {
+        const size_t want = std::min(A.block, cap - len);
+        if (!want) {                            // (a line longer than the slot's text: the host's block)
+            carry.assign(text, len);
+            fc2::samgrp::release(A.sam_stage, slot);
+            return 0;
+        }
+        if (A.wake[0] >= 0) {
+            pollfd pf[2] = {{h->fd, POLLIN, 0}, {A.wake[0], POLLIN, 0}};
+            int pr;
+            do { pr = poll(pf, 2, -1); } while (pr < 0 && errno == EINTR);
+            if (pr > 0 && pf[1].revents) {      // the ingest is closing
+                fc2::samgrp::release(A.sam_stage, slot);
+                return 2;
+            }
+        }
+        ssize_t k;
+        do { k = read(h->fd, text + len, want); } while (k < 0 && errno == EINTR);
+        if (k < 0) {
+            b.read_rc = FC2_E_IO;
+            b.read_err = std::string("read error: ") + strerror(errno);
+            in_eof = true;
+            break;
+        }
+        if (k == 0) in_eof = true;
+        else if (!has_nl) has_nl = memchr(text + len, '\n', (size_t)k) != nullptr;
+        len += (size_t)k;
+    }
+    carry.clear();
+    const char *nl = len ? (const char *)memrchr(text, '\n', len) : nullptr;
+    if (!in_eof) {                              // whole lines only; the rest starts the next block
+        carry.assign(nl + 1, (size_t)(text + len - (nl + 1)));   // (nl exists: the loop above read up to one)
+        len = (size_t)(nl + 1 - text);
+    } else {
+        b.eof = true;
+        if (b.read_rc) len = nl ? (size_t)(nl + 1 - text) : 0;   // a line cut short by the failed read is not a record
+    }
+    b.block.clear();
+    b.stext = text;
+    b.slen = len;
+    b.slot = slot;
+    b.rows = fc2::samgrp::submit(A.sam_stage, slot, (uint32_t)len);
+    return 1;
+}
+
 // splitter: the input from where the header ended, in newline-aligned numbered blocks
 // (A is handed over, not read from h->ahead: closing resets h->ahead before ~SamAhead joins, and a
 // thread that only starts running then must still find its object)
@@ -1369,7 +1467,22 @@ void sam_split_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
         b->read_rc = FC2_OK;
         b->read_err.clear();
         b->eof = false;
+        retire_slot(A, *b);
         std::string &blk = b->block;
+        if (A.sam_stage) {                      // fc2_ingest_set_gpu_sam_group: the block in a slot's text
+            const int how = sam_block_in_slot(h, A, *b, carry, in_eof);
+            if (how == 2) return;
+            if (how == 1) {
+                const bool last = b->eof;
+                {
+                    std::lock_guard<std::mutex> lk(A.m);
+                    A.todo.push_back(std::move(b));
+                }
+                A.cv.notify_all();
+                if (last) return;
+                continue;
+            }
+        }
         blk.swap(carry);
         carry.clear();
         // read until the block holds kBlock bytes and a newline, or the input ends
@@ -1643,8 +1756,8 @@ void sam_parse_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
             b = std::move(A.todo.front());
             A.todo.pop_front();
         }
-        const char *p = b->vbuf ? b->vbuf->data() + b->voff : b->block.data();
-        const char *end = p + (b->vbuf ? b->vlen : b->block.size());
+        const char *p = b->vbuf ? b->vbuf->data() + b->voff : b->stext ? b->stext : b->block.data();
+        const char *end = p + (b->vbuf ? b->vlen : b->stext ? b->slen : b->block.size());
         // the device's digest rows of a GPU-inflated batch: a cursor (BGZF block lj, its listed start
         // lk) steps through the lists beside the records, whose offsets only grow; a record takes its
         // row where a listed start is its own offset, the row is valid and carries its block_size
@@ -1724,10 +1837,61 @@ void sam_parse_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
             if (GpuInflate *gi = h->gpu_inflate.get()) gi->digest_dev_records += dig_dev, gi->digest_host_records += dig_host;
         h->group_dev_frags += grp_dev;
         b->lists.reset();
+        // SAM text whose rows a slot's launches made (fc2_ingest_set_gpu_sam_group): the lines' starts and their
+        // fragment rows, waited for here with a bound.  A line's number (lk) steps beside the lines; at a line
+        // start whose row says the device closed the fragment that opens there the loop steps to the line that
+        // opens the next one and leaves the placeholder the BAM branch above leaves, under its conditions: the
+        // batch already holds a real mapped record, the next fragment's first line lies in this block, and that
+        // this line closes the fragment before it is known from the rows (a placeholder ended exactly here) or
+        // from its name against the last mapped record's.
+        const uint32_t *sst = nullptr;
+        const fc2_bam_frag *sfr = nullptr;
+        uint32_t sn = 0, slk = 0;
+        if (!h->bam && b->rows) {
+            b->rows = false;
+            std::string err;
+            const fc2::samgrp::Wait w = fc2::samgrp::collect(A.sam_stage, b->slot, sst, sfr, sn, err);
+            if (w == fc2::samgrp::TIMED_OUT) {
+                b->rc = FC2_E_IO;
+                b->err = err + " (SAM text block " + std::to_string(b->seq) + ")";
+            }
+            if (w != fc2::samgrp::DONE || !A.group || h->need_text) sst = nullptr;
+        }
+        const char *const sbase = p;
+        bool sskip = sst != nullptr;
+        uint32_t run_lk = 0;
+        uint64_t sgrp_dev = 0;
         while (!h->bam && p < end && b->rc == FC2_OK) {
+            if (sskip && slk < sn && last_mapped != SIZE_MAX && sst[slk] == (uint32_t)(p - sbase)) {
+                const fc2_bam_frag &f = sfr[slk];
+                if (f.state == 1 && f.n_records >= 1 && (size_t)f.bytes < (size_t)(end - p) && slk + f.n_records < sn &&
+                    sst[slk + f.n_records] == sst[slk] + f.bytes) {
+                    bool closes = p == ph_end;
+                    if (!closes) {
+                        const char *tab = (const char *)memchr(p, '\t', (size_t)(end - p));
+                        const std::string &q = b->recs[last_mapped].qname;
+                        closes = tab && !(q.size() == (size_t)(tab - p) && memcmp(q.data(), p, q.size()) == 0);
+                    }
+                    if (closes) {
+                        if (b->n == b->recs.size()) b->recs.emplace_back();
+                        Rec &rec = b->recs[b->n];
+                        if (p != ph_end) run_p = p, run_n = b->n, run_lk = slk, run_cnt = 0;
+                        rec.ph = 1;
+                        rec.flag = 0;
+                        rec.ph_records = f.n_records, rec.ph_mates = f.n_mates, rec.ph_unmapped = f.n_unmapped;
+                        ++b->n;
+                        p += f.bytes;
+                        slk += f.n_records;
+                        ph_end = p;
+                        ++run_cnt, ++sgrp_dev;
+                        continue;
+                    }
+                }
+            }
             const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
             const char *ls = p, *le = nl ? nl : end;
             p = nl ? nl + 1 : end;
+            if (nl) ++slk;
             if (le > ls && le[-1] == '\r') --le;
             bool blank = true;
             for (const char *c = ls; c < le; ++c) if (!isspace((unsigned char)*c)) { blank = false; break; }
@@ -1735,9 +1899,20 @@ void sam_parse_loop(fc2_ingest *h, fc2_ingest::SamAhead *ap) {
             if (b->n == b->recs.size()) b->recs.emplace_back();
             b->recs[b->n].ph = 0;
             const int rc = parse_sam_record(h, ls, le, b->recs[b->n], ps, !h->need_text);
+            // A row's closer is a usable line, which parse_sam_record accepts, so this is unreachable while the
+            // rule and the parser agree.  Should they ever not, the fragments stepped over before the line are
+            // parsed after all, and the error is raised where it is with the feature off
+            if (rc && ls == ph_end) {
+                b->n = run_n, p = run_p, slk = run_lk, sgrp_dev -= run_cnt;
+                ph_end = nullptr;
+                sskip = false;
+                continue;
+            }
             if (rc) { b->rc = rc; b->err = fc2_last_error(); break; }
+            if (sskip && !b->recs[b->n].unmapped()) last_mapped = b->n;
             ++b->n;
         }
+        if (sgrp_dev) h->sam_group_dev_frags += sgrp_dev;
         if (b->rc == FC2_OK && b->read_rc) { b->rc = b->read_rc; b->err = b->read_err; }
         b->gs = b->gt = 0;
         if (A.group) group_batch(A.gp, *b);
@@ -1775,7 +1950,7 @@ Rec *next_ahead(fc2_ingest *h, int &rc) {
             std::lock_guard<std::mutex> lk(A.m);
             --A.inflight;
             if (A.pin) A.pinned.push_back(std::move(A.cur));
-            else A.spare.push_back(std::move(A.cur));
+            else { retire_slot(A, *A.cur); A.spare.push_back(std::move(A.cur)); }
         }
         A.cv.notify_all();
     }
@@ -2317,6 +2492,25 @@ extern "C" int fc2_ingest_group_counts(const fc2_ingest *h, uint64_t *device_fra
     return FC2_OK;
 }
 
+extern "C" int fc2_ingest_set_gpu_sam_group(fc2_ingest *h, int on, int device) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_sam_group: null argument");
+    if (on < 0 || on > 2 || device < 0) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_sam_group: on is 0, 1 or 2, device 0 or more");
+    if (h->bam) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_sam_group: the input is BAM (fc2_ingest_set_gpu_group is its stage)");
+    if (h->ahead) return fc2::fail(FC2_E_PARAM, "fc2_ingest_set_gpu_sam_group: call before reading");
+    h->sam_group = on;
+    h->sam_group_device = device;
+    return FC2_OK;
+}
+
+extern "C" int fc2_ingest_sam_group_counts(const fc2_ingest *h, uint64_t *device_fragments, uint64_t *host_fragments) {
+    if (!h) return fc2::fail(FC2_E_PARAM, "fc2_ingest_sam_group_counts: null argument");
+    // (meaningful at the end of the input, as fc2_ingest_group_counts)
+    const uint64_t dev = h->sam_group_dev_frags.load(), all = h->counts.n_reads;
+    if (device_fragments) *device_fragments = dev;
+    if (host_fragments) *host_fragments = all > dev ? all - dev : 0;
+    return FC2_OK;
+}
+
 // The fragment rows of every listed start, from the rule the kernel compiles (fc2_bam_frag_impl.h) over
 // digest rows made by fc2_bam_digest_host, with the blocks' status applied as bam_digest_kernel applies it
 extern "C" int fc2_bam_frag_host(const uint8_t *bytes, uint32_t n_bytes, const uint32_t *ooff, const uint32_t *isize,
@@ -2542,6 +2736,12 @@ extern "C" void fc2_ingest_close(fc2_ingest *h) {
         uint64_t dev = 0, host = 0;
         fc2_ingest_group_counts(h, &dev, &host);
         fprintf(stderr, "gpu group: %llu fragments closed on the device, %llu grouped on the host\n", (unsigned long long)dev,
+                (unsigned long long)host);
+    }
+    if (h->sam_group && getenv("FC2_CALLER_TIMING")) {
+        uint64_t dev = 0, host = 0;
+        fc2_ingest_sam_group_counts(h, &dev, &host);
+        fprintf(stderr, "gpu sam group: %llu fragments closed on the device, %llu grouped on the host\n", (unsigned long long)dev,
                 (unsigned long long)host);
     }
     if (h->bam_out) {
@@ -2776,6 +2976,19 @@ int fc2::ing::pull(fc2_ingest *h, const fc2_ingest_params *p, uint64_t max_frags
             if (atoi(pm) > 0) ap->max_pinned = (size_t)atoi(pm);
         if (const char *fe = getenv("FC2_PARSE_INFLIGHT"))
             if (atoi(fe) > 0) ap->max_inflight = (size_t)std::min(atoi(fe), 256);
+        // fc2_ingest_set_gpu_sam_group: a slot for every block in flight and a few for batches kept pinned, each
+        // with room for a block and what a read may add beyond it; a line takes 64 bytes of text or more where
+        // the rows suffice.  The slots' buffers are made as they are first taken
+        if (!h->bam && h->sam_group) {
+            const size_t text = std::min<size_t>(ap->block + std::max<size_t>(ap->block / 4, 65536), FC2_SAM_GROUP_MAX_TEXT);
+            std::string err;
+            ap->sam_stage = fc2::samgrp::open(h->sam_group, h->sam_group_device, (int)ap->max_inflight + 8, (uint32_t)text,
+                                              (uint32_t)(text / 64 + 16), 0, fc2::samenc::names_table(h->refs), err);
+            if (!ap->sam_stage) {
+                h->ahead.reset();
+                return fc2::fail(FC2_E_HIP, "fc2_ingest_set_gpu_sam_group: " + err);
+            }
+        }
         // BGZF BAM is cut into parse blocks in place in the inflated batches; plain and other gzip BAM
         // through the copying splitter
         ap->splitter = !h->bam                          ? std::thread(sam_split_loop, h, ap)
@@ -2810,7 +3023,7 @@ void fc2::ing::release(fc2_ingest *h) {
     auto &A = *h->ahead;
     {
         std::lock_guard<std::mutex> lk(A.m);
-        for (auto &b : A.pinned) A.spare.push_back(std::move(b));
+        for (auto &b : A.pinned) { retire_slot(A, *b); A.spare.push_back(std::move(b)); }
     }
     A.pinned.clear();
     A.cv.notify_all();

@@ -129,6 +129,19 @@ class NativeIngest:
         N.check(N.lib().fc2_ingest_group_counts(self.h, ctypes.byref(d), ctypes.byref(c)))
         return int(d.value), int(c.value)
 
+    def set_gpu_sam_group(self, on: int, device: int = 0):
+        """SAM text input: whether the parse threads step over the unspliced fragments that GPU `device` closed
+        in the blocks of text the splitter sent it (fc2_ingest_set_gpu_sam_group; 1), or group every line
+        themselves (0, the default).  2 is a test setting: the host twin fills the slots' rows.  Before
+        reading; a BAM input refuses it."""
+        N.check(N.lib().fc2_ingest_set_gpu_sam_group(self.h, int(on), int(device)))
+
+    def sam_group_counts(self) -> Tuple[int, int]:
+        """group_counts for set_gpu_sam_group."""
+        d, c = ctypes.c_uint64(), ctypes.c_uint64()
+        N.check(N.lib().fc2_ingest_sam_group_counts(self.h, ctypes.byref(d), ctypes.byref(c)))
+        return int(d.value), int(c.value)
+
     def close_bam_out(self):
         N.check(N.lib().fc2_ingest_close_bam_out(self.h))
 

@@ -75,7 +75,7 @@ class NativeCaller:
                  bam_out: str = "", reads_gz=None, inflate_device=None, inflate_after: int = 0,
                  gzip_device=None, gzip_tile: int = 0, gzip_timeout_s: float = 0.0, gpu_walk: bool = True,
                  gpu_digest: bool = False, gpu_group: int = 0, bam_device=None, gzip_level: int = 1,
-                 gzip_history: int = 0, gzip_search=None, gzip_passes=None, bam_encode=None):
+                 gzip_history: int = 0, gzip_search=None, gzip_passes=None, bam_encode=None, gpu_sam_group=0):
         o = copts
         # the strings must outlive the handle's open call (fc2_caller_open copies them)
         self._keep = [o.name.encode(), known_circ.encode() if known_circ else None,
@@ -103,6 +103,9 @@ class NativeCaller:
         self.gpu_walk = gpu_walk               # ... their BAM record starts listed there too (else by host threads)
         self.gpu_digest = gpu_digest           # ... and the listed records' derived fields computed there (else parsed)
         self.gpu_group = int(gpu_group)        # ... and the unspliced fragments closed there (2: on the host, a test setting)
+        # a SAM text input's unspliced fragments closed on a GPU: 0 off, 1 or (1, device), 2 the host twin (a test
+        # setting); a BAM input, a -B writer and everything else that does not group on the parse threads ignore it
+        self.gpu_sam_group = gpu_sam_group if isinstance(gpu_sam_group, tuple) else (int(gpu_sam_group), 0)
         self.gzip_device = gzip_device         # spliced_reads.fastq.gz compressed on this GPU (None: the worker threads)
         self.gzip_tile = gzip_tile             # ... in tiles of this many bytes (0: 32768), each a gzip member
         self.gzip_timeout_s = gzip_timeout_s   # ... waiting at most this long for the device (0: 60 s)
@@ -140,6 +143,8 @@ class NativeCaller:
             N.check(L.fc2_ingest_set_gpu_digest(ing, int(bool(self.gpu_digest))))
         if self.gpu_group:
             N.check(L.fc2_ingest_set_gpu_group(ing, self.gpu_group))
+        if self.gpu_sam_group[0] and self.format == "sam":
+            N.check(L.fc2_ingest_set_gpu_sam_group(ing, int(self.gpu_sam_group[0]), int(self.gpu_sam_group[1])))
         if self.reads_gz:
             path, level, threads, piece = self.reads_gz
             N.check(L.fc2_caller_set_reads_gz(self.h, path.encode(), int(level), int(threads), int(piece)))
@@ -203,6 +208,13 @@ class NativeCaller:
         d, c = ctypes.c_uint64(), ctypes.c_uint64()
         L = N.lib()
         N.check(L.fc2_ingest_group_counts(L.fc2_caller_ingest(self.h), ctypes.byref(d), ctypes.byref(c)))
+        return int(d.value), int(c.value)
+
+    def sam_group_counts(self):
+        """group_counts for gpu_sam_group (fc2_ingest_sam_group_counts); (0, n) without it."""
+        d, c = ctypes.c_uint64(), ctypes.c_uint64()
+        L = N.lib()
+        N.check(L.fc2_ingest_sam_group_counts(L.fc2_caller_ingest(self.h), ctypes.byref(d), ctypes.byref(c)))
         return int(d.value), int(c.value)
 
     def reads_gz_counts(self):

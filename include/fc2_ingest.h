@@ -357,6 +357,56 @@ int fc2_ingest_set_bam_out_encode_caps(fc2_ingest *h, uint32_t max_lines, uint32
 /* batches written as the device (mode 2: the host rule) returned them, and batches encoded line by line on
  * the host; final after fc2_ingest_close_bam_out (0, 0 while the stage is off) */
 int fc2_ingest_bam_encode_counts(const fc2_ingest *h, uint64_t *gpu_batches, uint64_t *host_batches);
+
+/* ---- unspliced fragments of SAM text closed on the GPU (csrc/fc2_sam_frag_impl.h, fc2_sam_group.hip) ----
+ * A block is n_bytes of text as the ingest's splitter cuts it: whole lines.  A *line* is the bytes from the
+ * block's start, or from the byte after a `\n`, up to the next `\n`; a tail with no `\n` is not listed.
+ * starts[0 .. n_lines]: line k is text[starts[k] .. starts[k + 1] - 1) (without its `\n`), starts[0] = 0.
+ * A line is *usable* (its head row has state 1) only if it does not end in `\r`, has at least 10 tabs, a QNAME
+ * of 1..254 bytes, a FLAG that is [0-9]{1,5} and at most 65535, and a CIGAR that is `*` or made only of bytes
+ * in [0-9MIDNSHP=X].  A usable line is one the ingest's parse_sam_record accepts, with the flag, the name and
+ * the refID the row gives: what strtoll would be asked about (a sign, a blank, 0x) is not usable.  A blank
+ * line is not usable.  tid is RNAME through the names' table (fc2_sam_names_table): `*` and unknown names -1. */
+typedef struct fc2_sam_head {
+    uint32_t flag;        /* FLAG */
+    int32_t  tid;         /* RNAME's index in the header, -1 for `*` or a name it does not hold */
+    uint32_t l_name;      /* QNAME's bytes: the line's first l_name */
+    uint32_t state;       /* 1: usable, the fields above are the host parser's; 0: not, and the row is all zeros */
+} fc2_sam_head;
+/* The text of one launch at most, the bytes of a listing segment, and the words of scratch a launch needs. */
+#define FC2_SAM_GROUP_MAX_TEXT (16u << 20)
+#define FC2_SAM_GROUP_SEG      1024u
+#define FC2_SAM_GROUP_SCRATCH(n_bytes) (((uint64_t)(n_bytes) + FC2_SAM_GROUP_SEG - 1) / FC2_SAM_GROUP_SEG + 1)
+/* One block on the device (all pointers device memory, text of any alignment; n_bytes at most
+ * FC2_SAM_GROUP_MAX_TEXT; scratch: FC2_SAM_GROUP_SCRATCH(n_bytes) words), five launches on `stream`: the `\n`
+ * of every FC2_SAM_GROUP_SEG-byte segment counted, the counts scanned (*n_lines_out), starts[0 .. n_lines]
+ * written, the head rows (a wavefront a line), the fragment rows (a lane a line).  frag_rows[k] is
+ * fc2_bam_frag's row for line k under fc2_bam_frag's five conditions, with "record" read as "line", "the record
+ * at its end" as line k + 1, "the listed start before" as line k - 1, and name equality as byte equality of the
+ * QNAMEs: at most 4 unmapped lines on the way back, at most FC2_BAM_FRAG_CAP lines forward; the block's first
+ * head, a fragment whose closer is not a listed line of this block and any unusable line on the way give state
+ * 0; bytes = starts[N] - starts[H].  When n_lines > cap only *n_lines_out is written: the block is the host's.
+ * Nothing outside [text, text + n_bytes) is read whatever the bytes hold; nothing but *n_lines_out,
+ * starts[0 .. min(n_lines, cap)], line_rows and frag_rows[0 .. n_lines) and the scratch is written. */
+int fc2_sam_group_launch(const uint8_t *text, uint32_t n_bytes, const uint32_t *names_table, uint32_t table_bytes,
+                         uint32_t *starts, fc2_sam_head *line_rows, fc2_bam_frag *frag_rows, uint32_t *n_lines_out,
+                         uint32_t cap, uint32_t *scratch, void *stream);
+/* The same rows from host memory by the same rule (the tests' oracle, and the ingest's stand-in at setting 2). */
+int fc2_sam_group_host(const uint8_t *text, uint32_t n_bytes, const uint32_t *names_table, uint32_t table_bytes,
+                       uint32_t *starts, fc2_sam_head *line_rows, fc2_bam_frag *frag_rows, uint32_t *n_lines_out,
+                       uint32_t cap);
+/* SAM text input: whether the parse threads step over the fragments those rows close (on = 1: the splitter
+ * reads every block into a slot's pinned text and queues the upload, the launches and the download of starts
+ * and frag_rows on the slot's stream on GPU `device`; the parse thread that takes the block waits for them, at
+ * most 60 seconds) or group every line themselves (0, the default).  on = 2 is a
+ * test setting for machines without a GPU: fc2_sam_group_host fills the slot's rows, through the same slots and
+ * the same parse-thread logic.  Call before reading.  A BAM input refuses it (FC2_E_PARAM).  Only where
+ * fragments are grouped on the parse threads: never with a -B writer or fc2_ingest_next's SAM text.  A device
+ * failure, no free slot, a block over a slot's text, or more lines than a slot's rows leave that block to the
+ * host as ever; a device that does not answer in time ends the run with FC2_E_IO and the block's number. */
+int fc2_ingest_set_gpu_sam_group(fc2_ingest *h, int on, int device);
+/* As fc2_ingest_group_counts, for the stage above: to be read once the input is exhausted. */
+int fc2_ingest_sam_group_counts(const fc2_ingest *h, uint64_t *device_fragments, uint64_t *host_fragments);
 #ifdef __cplusplus
 }
 #endif
